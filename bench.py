@@ -14,6 +14,11 @@ collectives included, through libvnr_amd.so (vnrAmdDist*, RCCL opened with dlope
 
 Untimed setup: generate the synthetic volume on the GPU, train the model (data parallel with an RCCL gradient exchange when
 N > 1), build the renderer.  Rank 0 prints ONE JSON line.
+A plain run does only that, the warm-up and the K timed frames.  `--full` adds the un-timed legs and checks behind them: PSNR and the frame
+against the ground-truth volume, the CPU baseline, the one-stream / brick-off / budget-table / train-while-render legs and, with N > 1, the
+kernel-event and per-rank legs.  `--dump-outputs DIR` writes the frame the last timed step computed as DIR/frame.npy ([fb, fb, 4] float32
+RGBA) and its statistics as DIR/frame_stats.npy (float64: n_samples, n_reference_slots, n_iterations, n_rays_hit).  Every input is seeded,
+so two builds can be compared output for output; the trained model carries the rounding order of the training step's float atomics.
 Other BASELINE configurations through the same program: C2 + C3 = `--size 128 --fb 512 --levels 8 --features 8
 --log2-hashmap-size 19 --hidden-layers 2 --per-level-scale 2 --train-steps 10000` (synthetic vortex field).
 """
@@ -54,6 +59,13 @@ def parse():
     p.add_argument("--probe-collectives", action="store_true",
                    help="internal (N > 1): meet the other ranks over RCCL, run the collective self-test, exit 0 / 3; bench.py starts itself in this "
                         "mode in a child process first, so that a transport that fails or hangs on a new installation costs a child, not the run")
+    p.add_argument("--full", action="store_true",
+                   help="also the un-timed legs and checks after the timed frames (PSNR, frame vs ground truth, CPU baseline, one-stream / brick-off / "
+                        "budget-table / interactive legs; N > 1: the kernel-event and per-rank legs); the --no-* options below leave single ones out")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last timed frame (frame.npy, float32 RGBA) and its statistics (frame_stats.npy, float64: "
+                        "n_samples, n_reference_slots, n_iterations, n_rays_hit) to DIR; a frame above 48 MiB is written as a fixed, seeded "
+                        "sample of its pixels (frame_sample.npy, frame_sample_index.npy: 48 MiB together)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-psnr", action="store_true")
     p.add_argument("--no-alone", action="store_true", help="skip the un-timed one-stream leg (roofline.alone)")
@@ -67,7 +79,30 @@ def parse():
     p.add_argument("--c5-dir", default="/tmp")
     p.add_argument("--mode", type=int, default=5, choices=(5, 6, 8, 9, 11, 12, 14, 15),
                    help="rendering mode: 5 = sample streaming (BASELINE metric, default), 8 = the same with gradient shading (4 evaluations per sample)")
-    return p.parse_args()
+    a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
+    return a
+
+
+DUMP_FRAME_MAX_BYTES = 48 << 20   # the frame's share of --dump-outputs (sample + its index when sampled), which writes at most 64 MB in all
+
+
+def dump_outputs(d, frame, stats):
+    """--dump-outputs: what the timed path handed out for its last step, as .npy files of DIR"""
+    if frame is None:
+        raise RuntimeError("--dump-outputs: the pipeline handed out no frame for the last timed step")
+    os.makedirs(d, exist_ok=True)
+    if frame.nbytes <= DUMP_FRAME_MAX_BYTES:
+        np.save(os.path.join(d, "frame.npy"), np.ascontiguousarray(frame, dtype=np.float32))
+    else:
+        px = frame.reshape(-1, frame.shape[-1])
+        n = DUMP_FRAME_MAX_BYTES // (px[0].nbytes + 8)   # each sampled pixel: its float32 channels + its float64 index
+        idx = np.sort(np.random.default_rng(20240611).choice(px.shape[0], n, replace=False))
+        np.save(os.path.join(d, "frame_sample.npy"), px[idx].astype(np.float32))
+        np.save(os.path.join(d, "frame_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(d, "frame_stats.npy"),
+            np.array([stats["n_samples"], stats["n_reference_slots"], stats["n_iterations"], stats["n_rays_hit"]], dtype=np.float64))
 
 
 def cpu_baseline(sv, nv, info, dims, tfn_np, cam, fb, mc, pls, hidden_layers, log2_T):
@@ -571,7 +606,23 @@ def main():
     train_loss = api.vnrNeuralVolumeGetTrainingLoss(nv)
     psnr = None
     if not a.no_psnr and ctx.rank == 0:
-        psnr = api.vnrNeuralVolumeGetPSNR(nv)
+        if a.full:
+            psnr = api.vnrNeuralVolumeGetPSNR(nv)
+        else:
+            # The PSNR pass makes one inference launch per 4096 x 16 x 16 block of the volume (csrc/volume.hip, NeuralVolume::get_psnr), each
+            # below the size that builds the small tier of the inference cache; once the library's policy has counted enough launches on
+            # unchanged parameters it builds the full image (tier 2), so on the bench volume the pass left that image built before the warm-up.
+            # A plain run reaches the same state with one-sample launches: it stops when the library reports tier 2, after the launches the
+            # policy says it waits for, or after as many launches as the pass would have made, whichever comes first.
+            blocks = int(np.prod([-(-n // min(b, n)) for n, b in zip(dims, (4096, 16, 16))]))
+            policy = api.neural_brick_image(nv)["launches_before_next_build"] + 1
+            point = np.full((1, 3), 0.5, np.float32)
+            for _ in range(min(blocks, policy)):
+                if api.neural_brick_image(nv)["tier"] == 2:
+                    break
+                api.neural_inference(nv, point)
+            if blocks >= policy and api.neural_brick_image(nv)["tier"] != 2:
+                print("[bench] the full inference cache was not built before the warm-up (refused by its budget or VNR_AMD_BRICK)", file=sys.stderr, flush=True)
 
     colors, alphas = syn.tfn_ramp_with_bumps(opacity_scale=a.opacity_scale)
     tfn = api.vnrCreateTransferFunction()
@@ -639,14 +690,16 @@ def main():
         sr.render()
         if k > 0:
             add(sr.completed_stats())
-    sr.flush()
+    last_frame = sr.flush()
     add(sr.completed_stats())
     st = sr.completed_stats()
     dist.barrier(ctx)
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs and ctx.rank == 0:
+        dump_outputs(a.dump_outputs, sr.download(last_frame), st)
     rays_hit = st["n_rays_hit"]
     samples_evt, evt_frames = samples, a.steps     # the frames the kernel events cover
-    if ctx.world > 1 and not a.no_kernel_events:   # un-timed: the same frames with the events on
+    if a.full and ctx.world > 1 and not a.no_kernel_events:   # un-timed: the same frames with the events on
         api.vnrRendererSetProfiling(ren, True)
         keep = (samples, slots, iters)
         samples = slots = 0
@@ -666,7 +719,7 @@ def main():
     # (N > 1, un-timed) where a rank's frame time goes, per rank, so that a bad scaling curve can be read from ONE record: the share alone
     # (vnrRender completes the rank's share, host-synchronous), then the gather (in-place all-gather + assembly, vnrAmdRendererGatherFrame)
     per_rank = None
-    if ctx.world > 1:
+    if a.full and ctx.world > 1:
         n_pr = max(5, min(a.steps // 2, 20))
         t_share = t_gather = 0.0
         for k in range(n_pr + 2):
@@ -694,7 +747,7 @@ def main():
 
     # ---- un-timed: the neural frame against the frame of the ground-truth volume (same camera / TFN / mode / macrocell) --------
     image = None
-    if ctx.world == 1 and not a.no_psnr:
+    if a.full and ctx.world == 1 and not a.no_psnr:
         def one_frame(volume):
             rr = make_renderer(volume, device_output=False, profiling=False)
             api.vnrRender(rr)
@@ -715,7 +768,7 @@ def main():
     # meant to be.
     n_leg = max(5, min(a.steps // 2, 30))
     alone = None
-    if ctx.world == 1 and not a.no_alone and os.environ.get("VNR_AMD_RENDER_HALVES", "2") != "1":
+    if a.full and ctx.world == 1 and not a.no_alone and os.environ.get("VNR_AMD_RENDER_HALVES", "2") != "1":
         os.environ["VNR_AMD_RENDER_HALVES"] = "1"
         ren1 = make_renderer(nv)
         del os.environ["VNR_AMD_RENDER_HALVES"]
@@ -725,7 +778,7 @@ def main():
     # (2) the same frames WITHOUT the brick image: what an application that trains while it renders gets (every optimizer step
     # drops the image, so it never exists there); the image costs `inference_cache.brick_image_bytes` of HBM
     brick_off = None
-    if ctx.world == 1 and not a.no_brick_off and brick_state["in_use"]:
+    if a.full and ctx.world == 1 and not a.no_brick_off and brick_state["in_use"]:
         check(L.vnrAmdNeuralVolumeSetBrickImageMode(nv.h, 0))
         ren2 = make_renderer(nv)
         fps2, b_samples, b_ms, b_launches, b_union = untimed_frames(ren2, n_leg)
@@ -742,7 +795,7 @@ def main():
     # (3) what a budget for the image buys: the hashed levels are taken finest first while they fit, so a budget is a number of levels.
     # One un-timed leg per budget, each a fresh renderer on the same model: frames/s (two streams) and the evaluation kernel's union fraction.
     budget_table = None
-    if ctx.world == 1 and not a.no_brick_table and not a.no_brick_off and brick_state["in_use"] and a.mode == 5:
+    if a.full and ctx.world == 1 and not a.no_brick_table and not a.no_brick_off and brick_state["in_use"] and a.mode == 5:
         budget_table = []
         full = int(brick_state["bytes"])
         for gb in (0.25, 0.75, 1.7, 3.8):
@@ -762,7 +815,7 @@ def main():
     # (4) the reference's interactive loop (apps/int_dual_volume.cpp:631-672): every displayed frame is followed by
     # vnrNeuralVolumeTrain(nv, train_steps, /*fast_mode=*/false) -- the optimizer steps plus, per step, the macrocell's update from the step's samples
     # and, per call, the refresh of its max-opacity (core/network.cu:231-259, 770-779).  This is the "instant" in instantvnr.  Un-timed for `value`.
-    interactive = interactive_leg(a, nv, make_renderer, brick_off) if ctx.world == 1 and not a.no_interactive and a.mode == 5 else None
+    interactive = interactive_leg(a, nv, make_renderer, brick_off) if a.full and ctx.world == 1 and not a.no_interactive and a.mode == 5 else None
 
     c5 = c5_leg(a, ctx) if a.c5 else None
 
@@ -796,7 +849,9 @@ def main():
                 "algorithmic_bytes_per_sample": bytes_per_sample, "flops_per_sample": flops_per_sample,
                 "avg_launch_ms": round(infer_ms / max(launches, 1), 4), "launches": launches,
                 "mfma_tflops": round(samples_evt * flops_per_sample / (infer_ms * 1e-3) / 1e12, 2) if infer_ms > 0 else 0.0}
-    if ctx.world > 1:
+    if ctx.world > 1 and not a.full:
+        roofline["events"] = "none: with more than one rank the HIP events around the launches stay out of the timed frames; --full measures them in an un-timed leg"
+    elif ctx.world > 1:
         roofline["events"] = (f"rank 0's launches in an un-timed leg of {evt_frames} frames behind the timed region: with more than one rank the HIP events "
                               "around every launch stay out of the timed frames (they cost 6 % of a 1/8 share's frame time)")
     # The renderer runs the rays as 2 halves on 2 streams by default (march of one half overlaps inference of the other,
@@ -1005,7 +1060,7 @@ def main():
         out["collective_self_test"] = self_test
         if transport_probe is not None:
             out["transport_probe"] = transport_probe
-    if ctx.world == 1 and not a.no_cpu_baseline:
+    if a.full and ctx.world == 1 and not a.no_cpu_baseline:
         mc = api.volume_macrocell(nv)
         out["cpu_baseline"] = cpu_baseline(sv, nv, info, dims, (colors, alphas), cam, a.fb, mc, pls, a.hidden_layers, a.log2_hashmap_size)
     print(json.dumps(out), flush=True)

@@ -166,3 +166,54 @@ def test_bare_gpus_2_without_a_device_fails_loudly_and_prints_no_line():
     out = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1"], {"VNR_AMD_DIST_TIMEOUT": "20"})
     assert out.returncode != 0 and not any(line.startswith("{") for line in out.stdout.splitlines()), out.stdout[-500:]
     assert "exited with code" in out.stderr
+
+
+def test_a_plain_run_leaves_the_extra_legs_to_full_and_steps_are_what_was_asked(bench, monkeypatch):
+    """`--full` is off by default (a plain run times the frames and prints the line; the un-timed legs and checks come with --full), the --no-*
+    options still parse beside it, and --steps sets the number of timed steps (at least one: ms_per_step is elapsed / steps)"""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.steps, a.warmup, a.dump_outputs) == (False, 7, 2, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline", "--no-interactive", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.no_cpu_baseline and a.no_interactive and a.dump_outputs == "d"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit) as e:
+        bench.parse()
+    assert e.value.code == 2
+
+
+def test_dump_outputs_writes_the_frame_and_its_statistics_within_64_mb(bench, tmp_path, monkeypatch):
+    """--dump-outputs: the last timed frame as frame.npy (float32) and its statistics as frame_stats.npy (float64); a frame above the cap is
+    written as the same seeded sample of its pixels every time, so two runs (or two builds) compare pixel for pixel"""
+    import numpy as np
+    frame = np.random.default_rng(3).random((48, 64, 4), dtype=np.float32)
+    stats = {"n_samples": 123456789012, "n_reference_slots": 5, "n_iterations": 24, "n_rays_hit": 3000, "infer_kernel_ms": 1.5}
+    bench.dump_outputs(str(tmp_path / "a"), frame, stats)
+    assert sorted(os.listdir(tmp_path / "a")) == ["frame.npy", "frame_stats.npy"]
+    got = np.load(tmp_path / "a" / "frame.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, frame)
+    st = np.load(tmp_path / "a" / "frame_stats.npy")
+    assert st.dtype == np.float64 and st.tolist() == [123456789012, 5, 24, 3000]
+    monkeypatch.setattr(bench, "DUMP_FRAME_MAX_BYTES", 24 * 100)    # 100 pixels of 16 bytes + their 8-byte indices
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), frame, stats)
+        assert sorted(os.listdir(tmp_path / d)) == ["frame_sample.npy", "frame_sample_index.npy", "frame_stats.npy"]
+    px, idx = np.load(tmp_path / "b" / "frame_sample.npy"), np.load(tmp_path / "b" / "frame_sample_index.npy")
+    assert px.shape == (100, 4) and px.dtype == np.float32 and idx.dtype == np.float64 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(px, frame.reshape(-1, 4)[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "frame_sample_index.npy"))
+    with pytest.raises(RuntimeError):
+        bench.dump_outputs(str(tmp_path / "d"), None, stats)
+
+
+@pytest.mark.parametrize("edge", [1024, 2048])
+def test_dump_outputs_stays_within_64_mb_at_bench_frame_sizes(bench, tmp_path, monkeypatch, edge):
+    """what --dump-outputs writes, added up file by file, for the default 1024^2 frame (written whole) and a 2048^2 one (sampled)"""
+    import numpy as np
+    frame = np.zeros((edge, edge, 4), np.float32)
+    stats = {"n_samples": 1, "n_reference_slots": 1, "n_iterations": 1, "n_rays_hit": 1}
+    bench.dump_outputs(str(tmp_path), frame, stats)
+    names = sorted(os.listdir(tmp_path))
+    assert names == (["frame.npy", "frame_stats.npy"] if edge == 1024 else ["frame_sample.npy", "frame_sample_index.npy", "frame_stats.npy"])
+    assert sum(os.path.getsize(tmp_path / n) for n in names) <= 64 * 10 ** 6

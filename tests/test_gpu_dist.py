@@ -279,7 +279,7 @@ def _bench_two_ranks(transport):
     import json
     port = _free_port()
     args = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--size", "64", "--fb", "256", "--levels", "6",
-            "--log2-hashmap-size", "14", "--hidden-layers", "2", "--train-steps", "120", "--no-psnr", "--no-cpu-baseline"]
+            "--log2-hashmap-size", "14", "--hidden-layers", "2", "--train-steps", "120", "--full", "--no-psnr", "--no-cpu-baseline"]
     procs = []
     for rank in range(2):
         env = dict(os.environ)
@@ -338,7 +338,7 @@ def test_bare_bench_gpus_2_starts_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "VNR_AMD_DIST_TRANSPORT", "VNR_RM_N_ITERS")}
     env["VNR_AMD_DIST_TIMEOUT"] = "120"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--size", "64", "--fb", "256", "--levels", "6",
-                          "--log2-hashmap-size", "14", "--hidden-layers", "2", "--train-steps", "120", "--no-psnr", "--no-cpu-baseline"],
+                          "--log2-hashmap-size", "14", "--hidden-layers", "2", "--train-steps", "120", "--full", "--no-psnr", "--no-cpu-baseline"],
                          env=env, capture_output=True, text=True, timeout=400)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-2500:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

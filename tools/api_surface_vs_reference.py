@@ -1,13 +1,14 @@
-"""Development-time check (this container only: it reads /root/reference/api.h as text): every function api.h declares, by name, number of
-parameters and the parameters' types (namespace prefixes, parameter names, defaults and white space dropped), is defined by
-include/vnr_api_shim.hpp with the same list.  usage: python tools/api_surface_vs_reference.py"""
+"""Development-time check: every function the reference's api.h declares, by name, number of parameters and the parameters' types
+(namespace prefixes, parameter names, defaults and white space dropped), is defined by include/vnr_api_shim.hpp with the same list, and its
+enumerations have the same enumerators in the same order.  The reference's side is read from tests/golden/reference_api_surface.json, which
+`--record` extracts from a checkout of the reference (its api.h), so that the check needs nothing outside this repository.
+usage: python tools/api_surface_vs_reference.py [--record REFERENCE_DIR]"""
+import json
 import os
 import re
 import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/api.h"
-if not os.path.exists(REF):
-    print("the reference is not here"); sys.exit(0)
+GOLDEN = os.path.join(ROOT, "tests", "golden", "reference_api_surface.json")
 
 
 def strip(text):
@@ -54,7 +55,34 @@ def signatures(text, definitions):
     return sigs
 
 
-ref = signatures(open(REF).read(), False)
+# the enumerations of api.h (rendering modes, value types): the same enumerators in the same order
+def enums(text):
+    out = {}
+    for m in re.finditer(r"\benum\s+(?:class\s+)?(\w+)\s*(?::\s*\w+\s*)?\{([^}]*)\}", strip(text)):
+        out[m.group(1)] = [e.split("=")[0].strip() for e in m.group(2).split(",") if e.strip()]
+    return out
+
+
+if len(sys.argv) == 3 and sys.argv[1] == "--record":
+    text = open(os.path.join(sys.argv[2], "api.h")).read()
+    sigs = signatures(text, False)
+    doc = {"what": "the reference's api.h as this check reads it: each declaration's name, parameter types and return type (namespace prefixes, "
+                   "parameter names and defaults dropped), and each enumeration's enumerators; written by tools/api_surface_vs_reference.py --record",
+           "functions": [{"name": n, "params": list(p), "returns": RETURNS[(False, (n, p))]} for n, p in sorted(sigs)],
+           "enums": enums(text)}
+    with open(GOLDEN, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    print(f"recorded {len(sigs)} declarations and {len(doc['enums'])} enumerations in {os.path.relpath(GOLDEN, ROOT)}")
+    sys.exit(0)
+if len(sys.argv) != 1:
+    sys.exit(__doc__)
+golden = json.load(open(GOLDEN))
+ref = set()
+for fn in golden["functions"]:
+    s = (fn["name"], tuple(fn["params"]))
+    ref.add(s)
+    RETURNS[(False, s)] = fn["returns"]
 shim = signatures(open(os.path.join(ROOT, "include", "vnr_api_shim.hpp")).read(), True)
 missing = sorted(s for s in ref if s not in shim)
 by_arity = {(n, len(p)) for n, p in shim}
@@ -70,15 +98,7 @@ hard += ret_diff
 print(f"{len(ref) - len(missing)} of {len(ref)} declarations have a definition with the same parameter types; {len(hard)} have none with that name and arity")
 
 
-# the enumerations of api.h (rendering modes, value types): the same enumerators in the same order
-def enums(text):
-    out = {}
-    for m in re.finditer(r"\benum\s+(?:class\s+)?(\w+)\s*(?::\s*\w+\s*)?\{([^}]*)\}", strip(text)):
-        out[m.group(1)] = [e.split("=")[0].strip() for e in m.group(2).split(",") if e.strip()]
-    return out
-
-
-ref_e, shim_e = enums(open(REF).read()), enums(open(os.path.join(ROOT, "include", "vnr_api_shim.hpp")).read())
+ref_e, shim_e = golden["enums"], enums(open(os.path.join(ROOT, "include", "vnr_api_shim.hpp")).read())
 for name, items in ref_e.items():
     ok = shim_e.get(name) == items
     hard += [] if ok else [name]

@@ -1,23 +1,35 @@
-"""Development-time check (this container only: it reads /root/reference as text): is the marching-cubes case table this library DERIVES
-(tools/gen_mc_table.py) the same surface, case by case, as the hand-made table the reference ships (core/marching_cube_constants.cuh)?
-Compared is what decides the surface's topology, its continuity across cells and its winding: the DIRECTED segments in which a case's
-triangles meet the six faces of the cell (pairs of cut edges), after mapping the reference's corner and edge numbering to this library's; the triangulation of a
-loop's interior is free.  usage: python tools/mc_table_vs_reference.py"""
+"""Development-time check: is the marching-cubes case table this library DERIVES (tools/gen_mc_table.py) the same surface, case by case, as
+the hand-made table the reference ships (core/marching_cube_constants.cuh)?  Compared is what decides the surface's topology, its continuity
+across cells and its winding: the DIRECTED segments in which a case's triangles meet the six faces of the cell (pairs of cut edges), after
+mapping the reference's corner and edge numbering to this library's; the triangulation of a loop's interior is free.  The reference's three
+tables are read from tests/golden/reference_mc_tables.npz, which `--record REFERENCE_DIR` writes from a checkout of the reference.
+usage: python tools/mc_table_vs_reference.py [--record REFERENCE_DIR]"""
 import os
 import re
 import sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import gen_mc_table as G  # noqa: E402
+import numpy as np  # noqa: E402
 
-path = "/root/reference/core/marching_cube_constants.cuh"
-if not os.path.exists(path):
-    print("the reference is not here"); sys.exit(0)
-text = open(path).read()
+GOLDEN = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "reference_mc_tables.npz")
+NAMES = ("MC_CASE_TABLE", "INDEX_TO_VERTEX", "EDGE_VERTICES")
+if len(sys.argv) == 3 and sys.argv[1] == "--record":
+    text = open(os.path.join(sys.argv[2], "core", "marching_cube_constants.cuh")).read()
+
+    def table(name):
+        body = re.search(name + r"\s*\[[^\]]*\]\s*=\s*\{([^}]*)\}", text).group(1)
+        return np.array([int(v) for v in re.findall(r"-?\d+", body)], np.int8)
+
+    np.savez(GOLDEN, **{n: table(n) for n in NAMES})
+    print(f"recorded {', '.join(NAMES)} in {os.path.relpath(GOLDEN)}")
+    sys.exit(0)
+if len(sys.argv) != 1:
+    sys.exit(__doc__)
+golden = np.load(GOLDEN)
 
 
 def table(name):
-    body = re.search(name + r"\s*\[[^\]]*\]\s*=\s*\{([^}]*)\}", text).group(1)
-    return [int(v) for v in re.findall(r"-?\d+", body)]
+    return [int(v) for v in golden[name]]
 
 
 cases, ref_corner, ref_edge = table("MC_CASE_TABLE"), table("INDEX_TO_VERTEX"), table("EDGE_VERTICES")
@@ -59,7 +71,6 @@ for c_ref, c_mine, amb, nr, nm in differ:
 
 # winding: for the eight cases with ONE corner inside, does a triangle's normal (right-hand rule over its vertex order, vertices at the cut
 # edges' midpoints) point away from that corner?
-import numpy as np  # noqa: E402
 mid = [(np.array(G.CORNERS[a], float) + np.array(G.CORNERS[b], float)) / 2 for a, b in G.EDGES]
 
 

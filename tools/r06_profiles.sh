@@ -9,8 +9,8 @@ O=$R/gpurun_out/r06_$T
 mkdir -p $O
 cd $R
 export TMPDIR=/tmp
-timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; python tools/bench_line.py $T < $O/bench.json
-(cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o b -- python3 $R/bench.py --no-cpu-baseline --no-psnr --no-brick-table --no-interactive) > $O/stats.log 2>&1; echo "stats rc=$?"
+timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; python tools/bench_line.py $T < $O/bench.json
+(cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o b -- python3 $R/bench.py --full --no-cpu-baseline --no-psnr --no-brick-table --no-interactive) > $O/stats.log 2>&1; echo "stats rc=$?"
 f=$(find $O/stats -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $O/bench_kernel_stats.csv && head -12 $O/bench_kernel_stats.csv | cut -c1-170
 t=$(find $O/stats -name "*kernel_trace.csv" | head -1)
 [ -n "$t" ] && python3 tools/leg_stats.py "$t" $O/bench "fused_infer_kernel<2, 32, 64, 0, false>" > $O/leg_stats.log 2>&1 && head -12 $O/bench_legs.txt

@@ -26,7 +26,6 @@ struct RenderParams {
   uint32_t tile_w_log2;                  // tile shape: 2^tile_w_log2 x 2^(6 - tile_w_log2) pixels (8x8, 16x4, 32x2 or 64x1)
   float bin_depth_rcp;                   // 1 / depth of one sample-sorting bin (world units)
   uint32_t tfn_in_lds;                   // the TFN tables fit in the march kernel's LDS
-  uint32_t no_ranks;                     // march_kernel: a sample's rank inside its depth bin is not kept in LDS (2 bytes per sample) but claimed again from the bin's counter
   uint32_t debug_flags;                  // diagnostics builds only (-DVNR_DIAG, VNR_AMD_DEBUG_FLAGS; read through dbg()): timing ablations that render garbage: 1 no compose, 2 no TFN, 4 no sort, 8 no DDA walk, 16 no sample records, 32 separate colour / opacity lookups
   vec3f cam_pos, cam_dir, cam_hor, cam_ver;
   affine3f wto;
@@ -163,11 +162,7 @@ __device__ __forceinline__ float adaptive_sampling_rate(float base_step, float m
 }
 __device__ __forceinline__ float opacity_correction(float step_rcp, float distance, float opacity)
 {
-#if defined(VNR_FAST_POW)   // experiment (tools/ab_build.sh fastpow -DVNR_FAST_POW): v_log_f32 / v_exp_f32 instead of the ~80 instructions of powf
-  return 1.0f - __builtin_amdgcn_exp2f(step_rcp * distance * __builtin_amdgcn_logf(1.0f - opacity));
-#else
   return 1.0f - __builtin_powf(1.0f - opacity, step_rcp * distance);
-#endif
 }
 __device__ __forceinline__ void write_pixel(const RenderParams& p, vec4f rgba, uint32_t pixel)
 {

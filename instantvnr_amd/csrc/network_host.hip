@@ -471,12 +471,11 @@ __global__ void __launch_bounds__(256) brick_build_rows_kernel(const LevelInfo l
 template <int F>
 static void launch_brick_build(const LevelInfo& lv, const uint16_t* table, uint8_t* image, uint64_t n_entries, hipStream_t s)
 {
-  static const bool rows = [] { const char* e = std::getenv("VNR_AMD_BRICK_BUILD_ROWS"); return !e || std::atoi(e) != 0; }();   // 0: the per-entry kernel (A/B, tests)
   constexpr uint32_t LX = F == 2 ? 3u : BrickShape<F>::lx, LY = F == 2 ? 1u : BrickShape<F>::ly, LZ = F == 2 ? 1u : BrickShape<F>::lz;
   const uint64_t res = lv.resolution;
   const uint32_t nbx = F == 2 ? lv.pad1 : (uint32_t)(res >> LX) + 1u, nby = (uint32_t)(res >> LY) + 1u, nbz = (uint32_t)(res >> LZ) + 1u;
   const size_t shmem = (size_t)(1u << (LY + LZ)) * ((res + 4) & ~(uint64_t)3) * F * 2;
-  if (rows && shmem <= 64 * 1024 && (uint64_t)nbx * nby * nbz * (128u / (F * 2)) == n_entries) {
+  if (shmem <= 64 * 1024 && (uint64_t)nbx * nby * nbz * (128u / (F * 2)) == n_entries) {
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((uint64_t)nby * nbz, 1u << 20);
     brick_build_rows_kernel<F><<<blocks, 256, shmem, s>>>(lv, (const half_t*)table, image, nbx, nby, nbz);
   } else {
@@ -488,8 +487,7 @@ static void launch_brick_build(const LevelInfo& lv, const uint16_t* table, uint8
 
 void Network::build_brick_image(hipStream_t s, bool small) const
 {
-  // which levels: the hashed ones (VNR_AMD_BRICK_DENSE=1: every level), finest first, while the image stays within the budget
-  static const bool dense_too = [] { const char* e = std::getenv("VNR_AMD_BRICK_DENSE"); return e && std::atoi(e) != 0; }();
+  // which levels: the hashed ones, finest first, while the image stays within the budget
   // Budget.  The image is a cache in memory nothing else of the process uses: a renderer that holds a 1024^3 fp32 volume (4.3 GB), its
   // 140 MB model and its frame buffers occupies 2 % of the 288 GB of an MI355X.  Default: 1/16 of the device's memory (18 GB), and never
   // more than a quarter of what is free when the image is built; VNR_AMD_BRICK_MAX_GB or vnrAmdNeuralVolumeSetBrickImageBudget set it.
@@ -521,7 +519,7 @@ void Network::build_brick_image(hipStream_t s, bool small) const
   const bool finest_first = F <= 2;
   for (int k = 0; k < (int)grid_.n_levels; ++k) {
     const int l = finest_first ? (int)grid_.n_levels - 1 - k : k;
-    if (lv[l].hashed >= 2u || (!lv[l].hashed && !dense_too)) continue;   // (a Tiled level repeats: nothing to de-hash)
+    if (lv[l].hashed != 1u) continue;   // (dense levels are not bricked; a Tiled level repeats: nothing to de-hash)
     if (brick_res_cap_ && lv[l].resolution > brick_res_cap_ + 1u) continue;
     const uint64_t res = lv[l].resolution;
     uint64_t n = ((res >> lx) + 1) * ((res >> ly) + 1) * ((res >> lz) + 1);
@@ -684,9 +682,7 @@ bool Network::inference_queue(const float* d_records, float* d_out, uint32_t out
 
 FusedMlp Network::fused_mlp() const
 {
-  // diagnostics: VNR_AMD_WEIGHTS_GLOBAL=1 reads the A operands of every 128-neuron model from global memory (what models beyond the LDS always do)
-  static const bool force_global = [] { const char* e = std::getenv("VNR_AMD_WEIGHTS_GLOBAL"); return e && std::atoi(e) != 0; }();
-  const bool wglobal = !weights_in_lds() || (force_global && cfg_.n_neurons == 128u);
+  const bool wglobal = !weights_in_lds();   // the A operands from global memory: a model whose weights do not fit the LDS
   return FusedMlp{mlp_packed_.ptr, lds_halves_, cfg_.n_neurons, n_hidden_matmuls(), cfg_.activation, cfg_.output_activation, !common_kind() || wglobal, wglobal,
                   cfg_.quantize_threshold};
 }

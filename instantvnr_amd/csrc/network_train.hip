@@ -617,7 +617,7 @@ __global__ void __launch_bounds__(256) grid_backward_persistent_kernel(const Gri
 // and a slice of the batch: it repeats the index arithmetic of every sample of its slice, adds the corners that fall into its tile
 // with LDS atomics (fp32: one rounding to the gradient's half precision at the end instead of one per update) and flushes the tile
 // with packed fp16 atomics on CONTIGUOUS entries, 16 entries per 64-byte request, skipping pairs nobody touched.  Requests per level:
-// slices x entries / 16 instead of 4 x batch.  Levels whose table needs more than VNR_AMD_GRID_BWD_LDS_TILES tiles, and hashed levels,
+// slices x entries / 16 instead of 4 x batch.  Levels whose table needs more than 64 tiles (grid_backward_plan), and hashed levels,
 // keep the global-atomic kernel.
 struct LdsBwdItem { uint32_t level, e0, e1, s0, s1; };   // entries [e0, e1) of `level`, samples [s0, s1)
 
@@ -892,21 +892,17 @@ void Network::reset_master_from_params(hipStream_t s)
 // which levels of the grid backward go through LDS tiles, and what the scatter costs in memory-side atomic requests (network.h)
 GridBackwardPlan Network::grid_backward_plan(size_t batch) const
 {
-  static const bool lds_bwd = [] { const char* e = std::getenv("VNR_AMD_GRID_BWD_LDS"); return !e || std::atoi(e) != 0; }();
-  static const uint32_t lds_kb = [] { const char* e = std::getenv("VNR_AMD_GRID_BWD_LDS_KB"); return e ? (uint32_t)std::max(8, std::min(144, std::atoi(e))) : 24u; }();
-  static const uint32_t lds_blocks = [] { const char* e = std::getenv("VNR_AMD_GRID_BWD_LDS_BLOCKS"); return e ? (uint32_t)std::max(1, std::atoi(e)) : 768u; }();
-  static const uint32_t lds_max_tiles = [] { const char* e = std::getenv("VNR_AMD_GRID_BWD_LDS_TILES"); return e ? (uint32_t)std::max(1, std::atoi(e)) : 64u; }();
   // (sweep of the three on the C4 model, profiles/r03_grid_backward_lds_sweep.txt: 24 KB tiles, ~768 blocks per level, levels of at most 64 tiles =
   // levels 0 - 4 of C4: grid backward 0.239 -> 0.18 - 0.22 ms, bimodal from run to run; larger tiles or more levels cost more in scanning
   // than their atomics saved)
+  constexpr uint32_t kLdsKb = 24, kLdsBlocks = 768, kLdsMaxTiles = 64;
   GridBackwardPlan p{};
   const uint32_t F = cfg_.n_features;
-  p.tile_entries = (lds_kb * 1024u / (4u * F)) & ~15u;
-  p.lds_blocks = lds_blocks;
+  p.tile_entries = (kLdsKb * 1024u / (4u * F)) & ~15u;
+  p.lds_blocks = kLdsBlocks;
   p.n_levels = n_active_levels();
-  if (lds_bwd)
-    while (p.lds_levels < p.n_levels && !grid_.levels[p.lds_levels].hashed && ((size_t)grid_.levels[p.lds_levels].offset * F) % 2 == 0 &&
-           div_round_up(grid_.levels[p.lds_levels].size, p.tile_entries) <= lds_max_tiles) ++p.lds_levels;   // (the flush adds aligned pairs of halves)
+  while (p.lds_levels < p.n_levels && !grid_.levels[p.lds_levels].hashed && ((size_t)grid_.levels[p.lds_levels].offset * F) % 2 == 0 &&
+         div_round_up(grid_.levels[p.lds_levels].size, p.tile_entries) <= kLdsMaxTiles) ++p.lds_levels;   // (the flush adds aligned pairs of halves)
   // memory-side requests of one step (MI355X_MICROARCH.md "Global float atomics": a wave instruction leaves L2 as 64-byte requests).  The atomic
   // kernel's lanes are (sample, x bit, feature pair) with the two x-neighbours of a corner pair adjacent: ONE request per (sample, level, yz corner)
   // while an entry pair fits 64 bytes; an LDS tile flushes at most (entries x F x element bytes) / 64 requests per slice of the batch.
@@ -929,7 +925,7 @@ void Network::scatter_grid_gradients(const float* d_coords, size_t batch, hipStr
   TrainScratch& ts = scratch_of(this);
   const uint32_t n = (uint32_t)batch;
   // 5. hash-grid backward: levels [l0, l1) per launch (blockIdx.y + l0 = level)
-  // levels [0, lds_levels) go through grid_backward_lds_kernel: dense, and at most kLdsBwdMaxTiles LDS tiles (VNR_AMD_GRID_BWD_LDS=0: none)
+  // levels [0, lds_levels) go through grid_backward_lds_kernel: dense, and at most 64 LDS tiles (grid_backward_plan)
   const GridBackwardPlan plan = grid_backward_plan(batch);
   const uint32_t tile_entries = plan.tile_entries, lds_levels = plan.lds_levels, lds_blocks = plan.lds_blocks;
   // n_features = 1: the scatter's target is the float image (fold_grid_grads_f32_kernel); the fold of a level range follows its scatter on the
@@ -990,9 +986,9 @@ void Network::scatter_grid_gradients(const float* d_coords, size_t batch, hipStr
     const uint32_t pairs = cfg_.n_features >= 2 ? cfg_.n_features / 2 : 1u;
     const dim3 g(div_round_up((uint64_t)batch * pairs * 2, 256), l1 - l0);  // one lane per (sample, x bit, feature pair)
     half_t* gg = (half_t*)grads_.ptr + n_mlp_;
-    if (side_by_side) {   // a few blocks per CU walk the same lanes (VNR_AMD_GRID_BWD_BLOCKS_PER_CU, default 2: swept 2 / 3 / 4 / 6 / 8, profiles/r05_train_overlap_ab.txt)
-      static const uint32_t per_cu = [] { const char* e = std::getenv("VNR_AMD_GRID_BWD_BLOCKS_PER_CU"); return e ? (uint32_t)std::max(1, std::min(16, std::atoi(e))) : 2u; }();
-      const uint32_t blocks = std::min<uint32_t>(g.x * g.y, (uint32_t)Runtime::get().n_cus * per_cu);
+    if (side_by_side) {   // a few blocks per CU walk the same lanes
+      constexpr uint32_t kBlocksPerCu = 2;   // (swept 2 / 3 / 4 / 6 / 8, profiles/r05_train_overlap_ab.txt)
+      const uint32_t blocks = std::min<uint32_t>(g.x * g.y, (uint32_t)Runtime::get().n_cus * kBlocksPerCu);
       switch (cfg_.n_features) {
       case 1: grid_backward_persistent_kernel<1><<<blocks, 256, 0, s>>>(grid_, d_coords, (const half_t*)ws_dfeat_.ptr, n, in_width_, gg32, l0, l1 - l0); break;
       case 2: grid_backward_persistent_kernel<2><<<blocks, 256, 0, s>>>(grid_, d_coords, (const half_t*)ws_dfeat_.ptr, n, in_width_, gg, l0, l1 - l0); break;

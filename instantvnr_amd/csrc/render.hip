@@ -28,23 +28,6 @@
 
 namespace vnr {
 
-// In-kernel stamps of the march kernel's phases (diagnostic builds only: tools/ab_build.sh <tag> -DVNR_MARCH_STAMPS; the guide's
-// "In-kernel stamps"): cycles per phase summed over the waves of every march_kernel<false> launch, read by tools/march_stamps.py
-#if defined(VNR_MARCH_STAMPS)
-__device__ unsigned long long g_march_stamps[16];
-// one record per wave-trip of the walk kernels' launch `it == 1` (plain stores: atomics on a few addresses from every wave of a launch
-// would themselves be what is measured): {s_memrealtime at the trip's start, at its end (100 MHz, one clock for the device), then
-// s_memtime differences of the trip's phases}
-constexpr uint32_t kWaveRecs = 65536;
-__device__ unsigned long long g_wave_rec[kWaveRecs][8];
-#define VNR_REALTIME(var) unsigned long long var; asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var) :: "memory")
-#define VNR_STAMP(var) unsigned long long var; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var) :: "memory")
-#define VNR_STAMP_ADD(slot, a, b) do { if (!FIRST && (threadIdx.x & 63u) == 0) atomicAdd(&g_march_stamps[slot], (b) - (a)); } while (0)
-#else
-#define VNR_STAMP(var)
-#define VNR_STAMP_ADD(slot, a, b)
-#endif
-
 // ------------------------------------------------------------------------------------------------ streaming march kernel
 // FIRST: thread = pixel of an 8x8 pixel tile (raygen, method_raymarching.cu:840-875) and emits the first batch.
 // !FIRST: thread = alive ray: compose the batch inferred last iteration (:732-838), then emit the next (:687-730).
@@ -65,21 +48,17 @@ __device__ unsigned long long g_wave_rec[kWaveRecs][8];
 // pass, one ray per pixel from that sample towards the light, alpha only, which finally shades and writes the pixel
 // (method_raymarching.cu:789-833, 877-900, 960-973).
 template <bool FIRST, int MODE>
-#if defined(VNR_MARCH_WAVES_PER_EU)   // experiment (tools/ab_build.sh m96 -DVNR_MARCH_WAVES_PER_EU=5): a march wave of 96 registers fits beside the evaluation kernel's four
-__attribute__((amdgpu_waves_per_eu(VNR_MARCH_WAVES_PER_EU, VNR_MARCH_WAVES_PER_EU)))   // waves of 104 on a SIMD; 232 bytes of scratch per lane; the frame 3.62 -> 3.93 ms
-#endif
 __global__ void __launch_bounds__(256) march_kernel(const RenderParams p, const RayList cur, const RayList nxt,
                                                     const vec2f* __restrict__ vd_in, vec4f* __restrict__ queue,
                                                     vec2f* __restrict__ vd_out, uint32_t* __restrict__ counters,
                                                     uint32_t* __restrict__ ray_counts, int parity, const SshLists ssh_lists,
                                                     uint32_t* __restrict__ tail_flag)
 {
-  extern __shared__ float s_t[];  // [n_iters][256] x {t0, t1}, histogram[256], claims[16], [n_iters][256] ranks (u16), then the transfer function tables
+  extern __shared__ float s_t[];  // [n_iters][256] x {t0, t1}, histogram[256], claims[16], then the transfer function tables
   float* s_t0 = s_t;
   float* s_t1 = s_t + (size_t)p.n_iters * 256;
   uint32_t* s_hist = (uint32_t*)(s_t + (size_t)2 * p.n_iters * 256);
   uint32_t* s_claim = s_hist + 256;             // [2][8]
-  uint16_t* s_rk = (uint16_t*)(s_claim + 16);   // rank of a sample inside its depth bin (< 64 n_iters); the bin is recomputed
   // the TFN tables are read 4x per composed sample: keep them in LDS (no TA traffic) when they fit
   DeviceTfn tfn = p.tfn;
   constexpr bool GRAD = MODE == M_GRADIENT;
@@ -87,7 +66,7 @@ __global__ void __launch_bounds__(256) march_kernel(const RenderParams p, const 
   tfn_lds_alphas_t lds_alphas = nullptr;
   bool tfn_merged = false;
   if (!FIRST && p.tfn_in_lds) {
-    vec4f* s_colors = (vec4f*)(s_rk + (p.no_ranks ? 0 : (size_t)p.n_iters * 256));
+    vec4f* s_colors = (vec4f*)(s_claim + 16);
     float* s_alphas = (float*)(s_colors + p.tfn.n_colors);
     tfn_merged = tfn_tables_to_lds(p.tfn, s_colors, s_alphas, !(dbg(p) & 32u));
     __syncthreads();
@@ -135,10 +114,6 @@ __global__ void __launch_bounds__(256) march_kernel(const RenderParams p, const 
       }
     };
 
-#if defined(VNR_MARCH_STAMPS)
-    VNR_REALTIME(rt0);
-#endif
-    VNR_STAMP(st0);
     if (active) {
       if (FIRST) {
         if (map_pixel(p, i, pixel)) {
@@ -182,8 +157,6 @@ __global__ void __launch_bounds__(256) march_kernel(const RenderParams p, const 
         if (MODE == M_SSH) { h_org = ssh_lists.org[0][i]; h_color = ssh_lists.color[0][i]; h_alpha = ssh_lists.alpha[0][i]; }
         m_dir = dir * p.mc_rcp;
         intersect_box(tmin, tmax, org, dir, p.bbox_lo, p.bbox_hi);
-        VNR_STAMP(st1);
-        VNR_STAMP_ADD(0, st0, st1);   // ray state loaded
         // compose (classification, opacity correction, front-to-back blending)
         // The results were written by the evaluation kernel on other CUs (other XCDs: their L2 is not ours), so a load of them
         // costs a trip to the fabric, and a loop that loads, classifies, blends and tests for saturation sample by sample pays
@@ -193,9 +166,6 @@ __global__ void __launch_bounds__(256) march_kernel(const RenderParams p, const 
         constexpr uint32_t kChunk = 8;
         const uint32_t sc_eff = (dbg(p) & 1u) ? 0u : sc;
         bool saturated = false;
-#if defined(VNR_MARCH_STAMPS)
-        unsigned long long acc_load = 0, acc_cls = 0, acc_blend = 0;
-#endif
         // the next chunk's results are requested before this chunk is classified: next to the evaluation kernels of the other ray
         // part a trip to the results takes ~8 us (stamped), and a batch is three chunks
         vec2f ahead[kChunk];
@@ -203,16 +173,10 @@ __global__ void __launch_bounds__(256) march_kernel(const RenderParams p, const 
         for (uint32_t j = 0; j < kChunk; ++j) ahead[j] = vd_in[sb + 64u * min(j, sc - 1u)];
         for (uint32_t k0 = 0; k0 < sc_eff && !saturated; k0 += kChunk) {
           vec2f chunk[kChunk];
-          VNR_STAMP(sc0);
 #pragma unroll
           for (uint32_t j = 0; j < kChunk; ++j) chunk[j] = ahead[j];
 #pragma unroll
           for (uint32_t j = 0; j < kChunk; ++j) ahead[j] = vd_in[sb + 64u * min(k0 + kChunk + j, sc - 1u)];
-#if defined(VNR_MARCH_STAMPS)
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          VNR_STAMP(sc1);
-          acc_load += sc1 - sc0;
-#endif
           // classification and opacity correction of the whole chunk first: eight independent instruction streams for the
           // scheduler to interleave (a march block runs one or two waves per SIMD, where a dependent instruction issues every
           // ~10 cycles and an independent one every 4); only the blend below is sequential
@@ -224,11 +188,6 @@ __global__ void __launch_bounds__(256) march_kernel(const RenderParams p, const 
             else tfn_sample(tfn, chunk[j].x, crgb[j], ca[j]);
             ca[j] = opacity_correction(p.step_rcp, chunk[j].y, ca[j]);
           }
-#if defined(VNR_MARCH_STAMPS)
-          asm volatile("" :: "v"(ca[0]), "v"(ca[7]), "v"(crgb[7].x));
-          VNR_STAMP(sc2);
-          acc_cls += sc2 - sc1;
-#endif
 #pragma unroll
           for (uint32_t j = 0; j < kChunk; ++j) {
             const uint32_t k = k0 + j;
@@ -257,28 +216,14 @@ __global__ void __launch_bounds__(256) march_kernel(const RenderParams p, const 
             if (MODE != M_SHADOW) { color.x += tr * rgb.x * a; color.y += tr * rgb.y * a; color.z += tr * rgb.z * a; }
             if (!(alpha < VNR_NEARLY_ONE)) { saturated = true; break; }
           }
-#if defined(VNR_MARCH_STAMPS)
-          asm volatile("" :: "v"(alpha), "v"(color.x));
-          VNR_STAMP(sc3);
-          acc_blend += sc3 - sc2;
-#endif
         }
-#if defined(VNR_MARCH_STAMPS)
-        VNR_STAMP_ADD(8, 0ull, acc_load); VNR_STAMP_ADD(9, 0ull, acc_cls); VNR_STAMP_ADD(10, 0ull, acc_blend);
-#endif
         alive = (alpha < VNR_NEARLY_ONE) && dda_resumable(it, m_dir, tmin, tmax, p.mc_dims);
         if (!alive) finish();
       }
     }
 
-    VNR_STAMP(st2);
-    VNR_STAMP_ADD(1, st0, st2);   // ... + compose
     // emit the next batch of this ray into LDS
     uint32_t k = 0;
-#if defined(VNR_MARCH_STAMPS)
-    uint32_t dbg_cells = 0;
-    const vec3i dbg_cell0 = it.cell;
-#endif
     if (alive && !(dbg(p) & 8u)) {
       const int n_iters = p.n_iters;
       iter_exec(p, it, m_dir, tmin, tmax, p.step, [&](float t0, float t1) -> bool {
@@ -287,21 +232,8 @@ __global__ void __launch_bounds__(256) march_kernel(const RenderParams p, const 
         return (int)(++k) < n_iters;
       });
       if (k == 0) finish();  // nothing left to sample: the ray is finished
-#if defined(VNR_MARCH_STAMPS)
-      dbg_cells = (uint32_t)(abs(it.cell.x - dbg_cell0.x) + abs(it.cell.y - dbg_cell0.y) + abs(it.cell.z - dbg_cell0.z));
-#endif
     }
-#if defined(VNR_MARCH_STAMPS)
-    {  // macrocell steps of this trip: the wave's longest ray, the sum over its rays, its alive rays
-      uint32_t mx = dbg_cells, sm = dbg_cells;
-      for (int d = 32; d > 0; d >>= 1) { mx = max(mx, (uint32_t)__shfl_xor((int)mx, d)); sm += (uint32_t)__shfl_xor((int)sm, d); }
-      const uint32_t n_alive = (uint32_t)__popcll(__ballot(alive));
-      VNR_STAMP_ADD(11, 0ull, (unsigned long long)mx); VNR_STAMP_ADD(12, 0ull, (unsigned long long)sm); VNR_STAMP_ADD(13, 0ull, (unsigned long long)n_alive);
-    }
-#endif
     const bool survive = alive && k > 0;
-    VNR_STAMP(st3);
-    VNR_STAMP_ADD(2, st2, st3);   // DDA walk + samples to LDS
 
     // wave64 compaction: rays by ballot, samples by prefix sum
     const unsigned long long mask = __ballot(survive);
@@ -344,8 +276,6 @@ __global__ void __launch_bounds__(256) march_kernel(const RenderParams p, const 
     uint32_t smp_base = claim[4];
     for (uint32_t w = 0; w < (tid >> 6); ++w) smp_base += claim[w];
     ++trip;
-    VNR_STAMP(st4);
-    VNR_STAMP_ADD(3, st3, st4);   // compaction, block-wide slot claim (two barriers)
     if (wave_rays == 0 || (dbg(p) & 16u)) continue;  // wave-uniform
 
     // depth bins of the group: front = smallest first-sample depth among the surviving rays
@@ -360,9 +290,7 @@ __global__ void __launch_bounds__(256) march_kernel(const RenderParams p, const 
       for (uint32_t j = 0; j < k; ++j) {
         const float t0 = s_t0[j * 256u + tid], t1 = s_t1[j * 256u + tid];
         const float t = (1.0f - jitter) * t0 + jitter * t1;
-        const uint32_t bin = depth_bin(p, t, front);
-        if (p.no_ranks) atomicAdd(&hist[bin], 1u);   // count only: the slot is claimed from the bin's counter when the record is written
-        else s_rk[j * 256u + tid] = (uint16_t)atomicAdd(&hist[bin], 1u);
+        atomicAdd(&hist[depth_bin(p, t, front)], 1u);   // count only: the slot is claimed from the bin's counter when the record is written
       }
     }
     __builtin_amdgcn_wave_barrier();
@@ -376,8 +304,6 @@ __global__ void __launch_bounds__(256) march_kernel(const RenderParams p, const 
     }
     hist[lane] = smp_base + hs - h;  // first gather-order slot of bin `lane`
     __builtin_amdgcn_wave_barrier();
-    VNR_STAMP(st5);
-    VNR_STAMP_ADD(4, st4, st5);   // depth-bin counting sort
 
     if (survive) {
       const uint32_t slot = (group << 6) + (uint32_t)__popcll(mask & lt_mask);
@@ -399,9 +325,10 @@ __global__ void __launch_bounds__(256) march_kernel(const RenderParams p, const 
         const float t0 = s_t0[j * 256u + tid], t1 = s_t1[j * 256u + tid];
         const float t = (1.0f - jitter) * t0 + jitter * t1;  // lerp(jitter, t0, t1), instantvnr_types.h:162-166
         const vec3f c = org + t * dir;
-        // gather-order slot: the bin's first slot + the sample's rank in the bin; without stored ranks the bin's counter is the next free slot
-        // (any order of a bin's samples will do: the evaluation of a sample does not depend on its neighbours in the queue)
-        const uint32_t g = p.no_ranks ? atomicAdd(&hist[depth_bin(p, t, front)], 1u) : hist[depth_bin(p, t, front)] + s_rk[j * 256u + tid];
+        // gather-order slot: the bin's counter is the next free slot of the bin (any order of a bin's samples will do: the evaluation
+        // of a sample does not depend on its neighbours in the queue).  No rank is kept in LDS (8 instead of 10 bytes per staged sample):
+        // the first march of a frame fits three blocks per CU instead of two, 200 -> 160 us (profiles/r05_march_occupancy.txt)
+        const uint32_t g = atomicAdd(&hist[depth_bin(p, t, front)], 1u);
         // one 16-byte record per evaluation: position + the float index of the result arena its value goes to
         if (GRAD) {
           const uint32_t gi = arena_grad_index(p.slot_cap, sb + 64u * j);
@@ -425,37 +352,9 @@ __global__ void __launch_bounds__(256) march_kernel(const RenderParams p, const 
       }
     }
     __builtin_amdgcn_wave_barrier();  // the LDS arrays are reused by the next loop trip
-    VNR_STAMP(st6);
-    VNR_STAMP_ADD(5, st5, st6);   // ray state + queue records + dt written
-    VNR_STAMP_ADD(6, st0, st6);   // the whole trip
-    VNR_STAMP_ADD(7, st0, st0 + 1ull);   // trips
-#if defined(VNR_MARCH_STAMPS)
-    if (!FIRST && lane == 0) {   // the longest trip of this group over the launches since the records were cleared (tools/wave_records.py)
-      VNR_REALTIME(rt1);
-      unsigned long long* rec = g_wave_rec[((p.il_part & 7u) << 13) | (group & 8191u)];
-      if (st6 - st0 > rec[7]) {
-        rec[0] = rt0; rec[1] = rt1; rec[2] = st2 - st0; rec[3] = st3 - st2; rec[4] = st4 - st3; rec[5] = st5 - st4; rec[6] = st6 - st5; rec[7] = st6 - st0;
-      }
-    }
-#endif
   }
 }
 
-#if defined(VNR_MARCH_STAMPS)
-extern "C" int vnrAmdDebugWaveRecords(unsigned long long* out, unsigned n_records, int reset)
-{
-  if (n_records > kWaveRecs) return 1;
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wave_rec), (size_t)n_records * 8 * sizeof(unsigned long long)) != hipSuccess) return 1;
-  if (reset) { void* d = nullptr; if (hipGetSymbolAddress(&d, HIP_SYMBOL(g_wave_rec)) != hipSuccess || hipMemset(d, 0, sizeof(g_wave_rec)) != hipSuccess) return 1; }
-  return 0;
-}
-extern "C" int vnrAmdDebugMarchStamps(unsigned long long* out16, int reset)
-{
-  if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_march_stamps), sizeof(g_march_stamps)) != hipSuccess) return 1;
-  if (reset) { unsigned long long z[16] = {}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_march_stamps), z, sizeof(z)); }
-  return 0;
-}
-#endif
 
 // iterative_sampling_groundtruth_kernel (method_raymarching.cu:902-915) over the compacted sample queue
 __global__ void gt_sample_kernel(const uint32_t* __restrict__ n_ptr, const float* __restrict__ vol, vec3i dims,
@@ -468,7 +367,7 @@ __global__ void gt_sample_kernel(const uint32_t* __restrict__ n_ptr, const float
   }
 }
 
-// pack_rays_block (pack_rays.h) as a kernel of its own: ground-truth volumes, models outside the MFMA kernels' shapes, VNR_AMD_FUSED_PACK=0
+// pack_rays_block (pack_rays.h) as a kernel of its own: ground-truth volumes, models outside the MFMA kernels' shapes, parts of more than 262 144 rays
 template <int WAVES>
 __global__ void __launch_bounds__(64 * WAVES) compact_rays_kernel(const PackArgs a)
 {
@@ -839,9 +738,6 @@ Renderer::Renderer(std::shared_ptr<VolumeBase> volume) : volume_(std::move(volum
 {
   if (!Runtime::get().ready()) Runtime::get().init(-1);
   stream_ = Runtime::get().stream;
-  // experiment (tools/two_renderers.py): a renderer whose part-0 chain does not share the runtime's stream with other renderers
-  if (const char* e = std::getenv("VNR_AMD_RENDERER_OWN_STREAM")) if (std::atoi(e) != 0) { VNR_HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking)); own_stream_ = true; }
-  if (const char* e = std::getenv("VNR_AMD_MARCH_RANKS")) march_ranks_ = std::atoi(e) != 0;
   if (const char* e = std::getenv("VNR_RM_N_ITERS")) { n_iters_ = std::max(1, std::min(48, std::atoi(e))); n_iters_fixed_ = true; }  // 2.5 KiB of LDS per iteration slot and block
   // streaming mode runs the rays as two halves on two streams (render_streaming); VNR_AMD_RENDER_HALVES=1: one stream
   if (const char* e = std::getenv("VNR_AMD_RENDER_HALVES")) { n_halves_ = std::max(1, std::min(kMaxParts, std::atoi(e))); n_halves_fixed_ = true; }
@@ -865,7 +761,6 @@ Renderer::Renderer(std::shared_ptr<VolumeBase> volume) : volume_(std::move(volum
 Renderer::~Renderer()
 {
   if (stream_) (void)hipStreamSynchronize(stream_);
-  if (own_stream_) (void)hipStreamDestroy(stream_);
   for (int i = 1; i < kMaxParts; ++i) if (part_streams_[i]) (void)hipStreamSynchronize(part_streams_[i]);   // (pool streams: not this renderer's to destroy)
   if (ev_fork_) (void)hipEventDestroy(ev_fork_);
   for (auto& ps : d_streams_) for (hipStream_t st : ps) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
@@ -1091,8 +986,8 @@ void Renderer::render()
 #if defined(VNR_DIAG)
   if (const char* e = std::getenv("VNR_AMD_DEBUG_FLAGS")) p.debug_flags = (uint32_t)std::atoi(e);
 #endif
-  static const float bin_depth = std::getenv("VNR_AMD_BIN_DEPTH") ? std::max(0.5f, (float)std::atof(std::getenv("VNR_AMD_BIN_DEPTH"))) : 8.0f;   // diagnostics (3 .. 8 measure the same)
-  p.bin_depth_rcp = 1.0f / bin_depth;  // 8 world units (voxels) per depth bin ~ the footprint of an 8x8 pixel tile
+  constexpr float kBinDepth = 8.0f;   // world units (voxels) per depth bin ~ the footprint of an 8x8 pixel tile (3 .. 8 measure the same)
+  p.bin_depth_rcp = 1.0f / kBinDepth;
   // camera, renderer.cpp:87-96
   const float t = 2.0f * tanf(camera_.fovy * 0.5f * (float)M_PI / 180.0f);
   const float aspect = (float)width_ / (float)height_;
@@ -1136,9 +1031,6 @@ void Renderer::render()
   // reference), so a frame assembled from such shares equals the unsharded frame rendered with VNR_RM_N_ITERS=32 bit for bit and
   // the unsharded frame at the default 24 to ~4e-5 on 0.2 % of the pixels (tests/test_gpu_fullsize.py); VNR_RM_N_ITERS pins both.
   p.n_iters = (!n_iters_fixed_ && (distributed_ || il_parts_ > 1) && p.n_local <= 262144u) ? 32 : n_iters_;
-  // A march block stages its batch in LDS: 8 bytes per sample, 10 with the depth sort's ranks (renderer.h march_ranks_: dropped by default
-  // in round 5, the slot inside a bin is claimed from the bin's counter when the record is written; same frames)
-  p.no_ranks = march_ranks_ ? 0u : 1u;
   // gradient shading (modes 7 / 8)
   p.otw = volume_->transform;
   p.grad_step = {1.0f / (float)p.vol_dims.x, 1.0f / (float)p.vol_dims.y, 1.0f / (float)p.vol_dims.z};  // object.cpp:305
@@ -1391,9 +1283,8 @@ void Renderer::launch_iteration(StreamingFrame& f, int h)
     // The march the previous frame ended with (it composes the last batch and finds no ray left to sample) is launched WITHOUT an
     // evaluation and a packing kernel behind it: both would be empty, and on a small share of the frame they are two more launches
     // on a chain of fifteen.  The march says in pinned memory whether a ray did survive; finish_streaming then launches the two
-    // kernels after all (launch_tail) and goes on as if they had been there.  VNR_AMD_TAIL_SKIP=0 switches this off (diagnostics).
-    static const bool tail_skip = [] { const char* e = std::getenv("VNR_AMD_TAIL_SKIP"); return !e || std::atoi(e) != 0; }();
-    const bool skip_tail = tail_skip && it >= 1 && it + 1 == f.predicted[h] && it + 1 < max_iterations;
+    // kernels after all (launch_tail) and goes on as if they had been there.
+    const bool skip_tail = it >= 1 && it + 1 == f.predicted[h] && it + 1 < max_iterations;
     uint32_t* tail_flag = nullptr;
     if (skip_tail) { hf.hs[0] = 0; tail_flag = hf.hs; }   // hs[0 .. C_HIT) is not used by the packing kernel's statistics
     // march(it): reads the dense ray list rl[0] (count: counter `parity`), leaves the survivors of every 64-ray group in the
@@ -1452,9 +1343,7 @@ void Renderer::launch_tail(StreamingFrame& f, int h, uint32_t it, hipStream_t s_
     // Only where the launch it saves is on the critical path, i.e. a part of at most 262 144 rays (a 1/2 .. 1/8 share of the bench frame):
     // a whole frame's packing kernel runs under the other part's evaluation kernel, the frame takes the same time either way, and the
     // evaluation kernel's own time (what bench.py's roofline is computed from) would carry the packing's 15-20 us per launch.
-    // VNR_AMD_FUSED_PACK=0 / 2: never / always (diagnostics).
-    static const int fused_pack_mode = [] { const char* e = std::getenv("VNR_AMD_FUSED_PACK"); return e ? std::atoi(e) : 1; }();
-    const bool fused_pack = fused_pack_mode == 2 || (fused_pack_mode == 1 && P <= 262144u);
+    const bool fused_pack = P <= 262144u;
     bool packed = false;
     if (!s_it) s_it = hf.s;
     if (profiling_) VNR_HIP_CHECK(hipEventRecord(events_[f.slot][h][2 * it], s_it));
@@ -1477,8 +1366,8 @@ void Renderer::launch_tail(StreamingFrame& f, int h, uint32_t it, hipStream_t s_
     if (!packed) {
       // 1024-thread blocks need 4 free wave slots on every SIMD of one CU at once, which the other half's evaluation kernel
       // rarely leaves: a small share (where the wait shows) packs with 256-thread blocks
-      static const uint32_t small_limit = [] { const char* e = std::getenv("VNR_AMD_COMPACT_SMALL_LIMIT"); return e ? (uint32_t)std::atoll(e) : 262144u; }();  // diagnostics
-      if (P <= small_limit) {
+      constexpr uint32_t kCompactSmallLimit = 262144u;
+      if (P <= kCompactSmallLimit) {
         compact_rays_kernel<4><<<pk.n_blocks, 256, 0, s_it>>>(pk);
       } else {
         pk.n_blocks = div_round_up(P, 1024);
@@ -1588,7 +1477,7 @@ void Renderer::render_streaming(const RenderParams& p_all, int pass_mode, bool d
     VNR_HIP_CHECK(hipEventRecord(ev_fork_, stream_));
     for (int h = 1; h < H; ++h) VNR_HIP_CHECK(hipStreamWaitEvent(part_streams_[h], ev_fork_, 0));
   }
-  const size_t shmem = ((size_t)2 * p_all.n_iters + 1) * 256 * sizeof(float) + 16 * sizeof(uint32_t) + (p_all.no_ranks ? 0 : (size_t)p_all.n_iters * 256 * sizeof(uint16_t));
+  const size_t shmem = ((size_t)2 * p_all.n_iters + 1) * 256 * sizeof(float) + 16 * sizeof(uint32_t);
   const size_t shmem_compose = shmem + (p_all.tfn_in_lds ? (size_t)p_all.tfn.n_colors * sizeof(vec4f) + (size_t)p_all.tfn.n_alphas * sizeof(float) : 0);
   if (shmem_compose > 160 * 1024) throw std::runtime_error("VNR_RM_N_ITERS too large for the LDS of one workgroup");
   static bool lds_attr_set = false;
@@ -1780,10 +1669,9 @@ void Renderer::render_decoupled(const RenderParams& p_all, bool defer)
   }
   // The walks are the frame's critical path (a chain of launches whose duration is the latency of one wave) and the evaluation kernel
   // fills every wave slot it is given: the walk and compose streams are created with the highest priority, the evaluation streams with
-  // the lowest, so that a slot an evaluation block leaves goes to a waiting walk block first (VNR_AMD_DECOUPLED_PRIO=0: all equal)
-  static const bool prio = [] { const char* e = std::getenv("VNR_AMD_DECOUPLED_PRIO"); return !e || std::atoi(e) != 0; }();
+  // the lowest, so that a slot an evaluation block leaves goes to a waiting walk block first
   int prio_least = 0, prio_greatest = 0;
-  if (prio) VNR_HIP_CHECK(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
+  VNR_HIP_CHECK(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
   for (int h = 0; h < H; ++h)
     for (int k = 0; k < 3; ++k)
       if (!d_streams_[h][k]) VNR_HIP_CHECK(hipStreamCreateWithPriority(&d_streams_[h][k], hipStreamNonBlocking, k == 1 ? prio_least : prio_greatest));

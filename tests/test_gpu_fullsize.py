@@ -281,7 +281,7 @@ def test_a_rank_s_share_of_the_c4_frame_equals_the_oracle(oracle, c4_scene, monk
     within 0.2 %, PSNR > 90 dB / 1e-3; with the library's network values in the oracle's marcher PSNR > 120 dB / 1e-5."""
     import time
     monkeypatch.delenv("VNR_RM_N_ITERS", raising=False)
-    for k in ("VNR_AMD_SMALL_SHARE_PARTS", "VNR_AMD_RENDER_HALVES", "VNR_AMD_FUSED_PACK", "VNR_AMD_DECOUPLED"):
+    for k in ("VNR_AMD_SMALL_SHARE_PARTS", "VNR_AMD_RENDER_HALVES", "VNR_AMD_DECOUPLED"):
         monkeypatch.delenv(k, raising=False)
     nv = c4_scene["nv"]
     frame(c4_scene, 5, frames=3)                     # the de-hashed image is in use, as in the bench

@@ -1,7 +1,7 @@
-"""GPU box, experiment: what two frames IN FLIGHT would buy.  N renderers on streams of their own render the same share of the bench frame
-in turn with pipelined calls (each accumulates its own buffer: not the product's semantics, but the GPU sees what it would see if frame k + 1
-ran beside frame k instead of behind it); frames per second summed over the renderers against one renderer.
-usage: VNR_AMD_RENDERER_OWN_STREAM=1 python tools/two_renderers.py [shares=1,8] [renderers=1,2,3]"""
+"""GPU box, experiment: what two frames IN FLIGHT would buy.  N renderers (their part-0 chains on the runtime's stream) render the same share of the
+bench frame in turn with pipelined calls (each accumulates its own buffer: not the product's semantics, but the GPU sees what it would see if frame
+k + 1 ran beside frame k instead of behind it); frames per second summed over the renderers against one renderer.
+usage: python tools/two_renderers.py [shares=1,8] [renderers=1,2,3]"""
 import ctypes as C
 import os
 import sys

@@ -227,6 +227,16 @@ int      vnrAmdNeuralVolumeBrickImagePolicy(vnrAmdVolume, uint64_t* builds, unsi
  * out_u64 = {memory-side atomic requests of the global-atomic kernel, upper bound of the LDS tiles' flush requests}: what bench.py's
  * train_roofline is priced with (no restatement of these rules outside the library) */
 int      vnrAmdNeuralVolumeGridBackwardPlan(vnrAmdVolume, uint64_t batch, uint32_t out_u32[4], uint64_t out_u64[2]);
+/* AMD extension: deterministic training.  On, the hash-grid part of the gradient is summed in 64-bit fixed point (exponent per call from
+ * max |dL/dfeature|, one rounding per term, one fp16 rounding per entry: DESIGN.md 4.3), so the same seed, parameters and batches give the same
+ * bits on every run: vnrNeuralVolumeTrain (GPU sampler; out-of-core with its synchronous refresh), TrainBegin / TrainEnd and ForwardBackward,
+ * with VNR_AMD_TRAIN_OVERLAP on or off (the same bits either way), and data-parallel training over the shm transport.  Not covered: RCCL's
+ * fp16 sums, VNR_AMD_OOC_ASYNC=1.  Costs an int64 image of the grid part (8 bytes per grid parameter, allocated by the first deterministic step)
+ * and a slower grid backward.  A batch whose dL/dfeatures hold inf / NaN writes NaN to every grid entry of the active levels.  A runtime
+ * property: params.json does not carry it.  Off by default; VNR_AMD_DETERMINISTIC=1 makes it the default of volumes created afterwards.
+ * GridBackwardPlan reports the form that will run (8-byte elements, the deterministic tile size). */
+int      vnrAmdNeuralVolumeSetDeterministicTraining(vnrAmdVolume, int enable);
+int      vnrAmdNeuralVolumeGetDeterministicTraining(vnrAmdVolume, int* enabled);
 /* AMD extension (measurement): HIP events around the kernels of the training step; GetTrainProfile averages the last <= 64 steps:
  * ms_per_step = {forward, loss + MLP backward, weight gradients, grid backward (+ the exchange's pack kernels), optimizer} */
 int    vnrAmdNeuralVolumeSetTrainProfiling(vnrAmdVolume, int enable);
@@ -261,7 +271,8 @@ int    vnrAmdNeuralVolumeTrainEnd(vnrAmdVolume, float grad_scale, int fast_mode)
 int    vnrAmdNeuralVolumeForwardBackward(vnrAmdVolume, size_t n, const float* d_coords, const float* d_targets);
 /* Inspection of the last ForwardBackward / TrainBegin (tests/diag/grad_hammer.py; passive: no other call depends on them).
  * TrainingBuffer: device pointer + size of 0 the fp16 gradient blob, 1 dL/dfeatures [n][padded_width] fp16, 2 the encoded features,
- * 3 the hidden activations.  RescatterGridGradients: clears the hash-grid part of the blob and repeats the grid backward alone on the
+ * 3 the hidden activations, 4 the int64 image of the grid part that deterministic training sums into (zero between steps; 0 bytes before the
+ * first deterministic step).  RescatterGridGradients: clears the hash-grid part of the blob and repeats the grid backward alone on the
  * stored dL/dfeatures (same d_coords as the ForwardBackward it repeats).  GradientDistance: out4 = {sum (g - ref)^2, sum ref^2} over
  * the MLP part, then over the grid part, against an fp16 reference blob on the device, reduced on the device on the training stream. */
 int    vnrAmdNeuralVolumeTrainingBuffer(vnrAmdVolume, int which, const void** d_ptr, size_t* bytes);

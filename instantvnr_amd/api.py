@@ -609,6 +609,19 @@ def neural_grid_backward_plan(v, batch=65536):
     return {"n_levels": u32[0], "lds_levels": u32[1], "tile_entries": u32[2], "lds_blocks": u32[3], "atomic_requests": int(u64[0]), "flush_requests_at_most": int(u64[1])}
 
 
+def neural_set_deterministic_training(v, enable=True):
+    """deterministic training (vnrAmdNeuralVolumeSetDeterministicTraining): the hash-grid gradient is summed in 64-bit fixed point, so
+    the same seed, parameters and batches train to the same bits on every run; off by default (VNR_AMD_DETERMINISTIC=1 changes that
+    default for volumes created afterwards)"""
+    check(lib().vnrAmdNeuralVolumeSetDeterministicTraining(v.h, 1 if enable else 0))
+
+
+def neural_get_deterministic_training(v):
+    e = C.c_int()
+    check(lib().vnrAmdNeuralVolumeGetDeterministicTraining(v.h, C.byref(e)))
+    return bool(e.value)
+
+
 def neural_level_table(v):
     """the hash grid's levels as the library laid them out: list of dicts(res, entries, offset, kind) (kind: 0 dense, 1 hash, 2-4 tiled)"""
     a = [np.zeros(32, np.uint32) for _ in range(4)]

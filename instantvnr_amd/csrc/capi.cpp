@@ -996,6 +996,17 @@ int vnrAmdNeuralVolumeGridBackwardPlan(vnrAmdVolume v, uint64_t batch, uint32_t 
     if (out_u64) { out_u64[0] = p.atomic_requests; out_u64[1] = p.flush_requests_at_most; }
   });
 }
+int vnrAmdNeuralVolumeSetDeterministicTraining(vnrAmdVolume v, int enable)
+{
+  return guarded([&]() { as_neural(v)->network().set_deterministic(enable != 0); });
+}
+int vnrAmdNeuralVolumeGetDeterministicTraining(vnrAmdVolume v, int* enabled)
+{
+  return guarded([&]() {
+    const bool e = as_neural(v)->network().deterministic();
+    if (enabled) *enabled = e ? 1 : 0;
+  });
+}
 int vnrAmdNeuralVolumeSetTrainProfiling(vnrAmdVolume v, int e) { return guarded([&]() { as_neural(v)->network().set_train_profiling(e != 0); }); }
 int vnrAmdNeuralVolumeGetTrainProfile(vnrAmdVolume v, double ms_per_step[5], int* n_steps)
 {

@@ -188,6 +188,12 @@ public:
   // a full optimizer step on such a state would be wrong and throws
   void set_opt_sharded(bool e) { opt_sharded_ = e; }
   bool opt_sharded() const { return opt_sharded_; }
+  // Deterministic training: the grid backward sums in 64-bit fixed point in every form it takes (plain, persistent, LDS tiles,
+  // exchange buckets), so the gradient is the same bits whatever order its atomics arrive in.  A runtime property, not part of params.json;
+  // VNR_AMD_DETERMINISTIC=1 makes it the default of networks created afterwards.  Off: the production kernels, untouched.
+  void set_deterministic(bool e) { deterministic_ = e; }
+  bool deterministic() const { return deterministic_; }
+  static bool deterministic_default();
   // the parameter ranges a data-parallel step exchanges, in the order forward_backward hands them over: the MLP, then the hash-grid
   // levels from the finest to the coarsest in buckets of at least `bucket` parameters (levels [first, second) each)
   std::vector<std::pair<uint32_t, uint32_t>> exchange_level_buckets(size_t bucket) const;
@@ -196,7 +202,7 @@ public:
   size_t level_range_hi(uint32_t level_end) const { return n_mlp_ + ((size_t)grid_.levels[level_end - 1].offset + grid_.levels[level_end - 1].size) * cfg_.n_features; }
   // Diagnostics of the training step (tests/diag/grad_hammer.py; passive: nothing else depends on them).  training_buffer: device
   // pointer and size of 0 the fp16 gradient blob, 1 dL/dfeatures [n][padded_width] fp16, 2 the features, 3 the hidden activations
-  // of the last forward_backward.  rescatter_grid_gradients: clears the grid part of the blob and repeats step 5 alone on the stored
+  // of the last forward_backward, 4 the deterministic mode's int64 image of the grid part.  rescatter_grid_gradients: clears the grid part of the blob and repeats step 5 alone on the stored
   // dL/dfeatures.  gradient_distance: {sum (g - ref)^2, sum ref^2} of the MLP part and of the grid part against an fp16 reference blob,
   // reduced on the device on stream s (what the blob holds BEFORE any download).
   const void* training_buffer(int which, size_t* bytes) const;
@@ -251,6 +257,7 @@ private:
   uint64_t steps_ = 0;
   uint64_t params_generation_ = 0;
   bool opt_sharded_ = false;
+  bool deterministic_ = deterministic_default();
   float lr_ = 0.0f;   // current learning rate (ExponentialDecay state); reset by configure() like the reference's rebuilt optimizer (tcnn_network.h:195-209)
 
   DeviceBuffer<uint16_t> params_f16_{MemTag::Network};   // tcnn-order blob (inference + serialisation)

@@ -685,6 +685,197 @@ __global__ void __launch_bounds__(256) grid_backward_lds_kernel(const GridDevice
   }
 }
 
+// ------------------------------------------------------------------------------------------------ deterministic grid backward
+// Opt-in (Network::set_deterministic): the same scatter in 64-bit FIXED POINT, so that the sums do not depend on the order in
+// which the adds arrive.  Once per call, M = max |dL/dfeature| over the batch's rows and the active levels' columns (an integer atomicMax on
+// the fp16 bit pattern of |g|, order-independent) gives the exponent e = floor(62 - log2(8 n M)): a sample adds at most 8 terms of weight <= 1
+// to one entry, so no entry's sum leaves int64.  A term is the fp32 product w * g the production kernels form, times 2^e (exact), rounded
+// to the nearest integer and added with a 64-bit integer atomic into an int64 image of the grid part; fold_grid_grads_det_kernel adds
+// sum * 2^-e to the fp16 blob.  The exponent lives in a device word (DetScale), so the step keeps no host synchronisation.
+struct DetScale {
+  uint32_t max_bits;   // max over the batch of the fp16 bits of |dL/dfeature|
+  int32_t e;           // the exponent, or kDetNothing / kDetNonFinite
+};
+constexpr int32_t kDetNothing = -0x7fffffff - 1;   // M = 0: nothing is scattered
+constexpr int32_t kDetNonFinite = 0x7fffffff;      // M is inf / NaN: the fold writes NaN over its whole range
+
+// columns [0, n_cols) of dfeat [n][in_width] (in_width a multiple of 8): 16-byte row segments, grid-stride; a block max, one atomicMax per block
+// (one per wave: 4 096 atomics on one word, 48 us at C4)
+__global__ void __launch_bounds__(256) grid_grad_scale_kernel(const half_t* __restrict__ dfeat, uint32_t n, uint32_t in_width, uint32_t n_cols,
+                                                              DetScale* __restrict__ det)
+{
+  const uint32_t segs = in_width / 8u;
+  const uint64_t total = (uint64_t)n * segs;
+  uint32_t m = 0;
+  for (uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t c0 = (uint32_t)(q % segs) * 8u;
+    if (c0 >= n_cols) continue;
+    const uint4_t v = *(const uint4_t*)(dfeat + q * 8u);
+    const uint32_t w[4] = {v[0], v[1], v[2], v[3]};
+#pragma unroll
+    for (uint32_t j = 0; j < 8u; ++j) {
+      const uint32_t bits = (w[j >> 1] >> (16u * (j & 1u))) & 0x7fffu;   // |g|: the order of the bit patterns is the order of the magnitudes
+      if (c0 + j < n_cols) m = max(m, bits);
+    }
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d));
+  __shared__ uint32_t wave_max[4];
+  if ((threadIdx.x & 63u) == 0) wave_max[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    m = max(max(wave_max[0], wave_max[1]), max(wave_max[2], wave_max[3]));
+    if (m) atomicMax(&det->max_bits, m);
+  }
+}
+
+__global__ void grid_grad_exponent_kernel(DetScale* __restrict__ det, uint32_t n)
+{
+  const uint32_t bits = det->max_bits;
+  if (bits == 0u) { det->e = kDetNothing; return; }
+  if (bits >= 0x7c00u) { det->e = kDetNonFinite; return; }
+  const uint16_t hb = (uint16_t)bits;
+  half_t mh;
+  __builtin_memcpy(&mh, &hb, 2);
+  int k;
+  const double f = frexp(8.0 * (double)n * (double)(float)mh, &k);   // 8 n M = f 2^k exactly, f in [0.5, 1)
+  det->e = 62 - (f == 0.5 ? k - 1 : k);                               // 62 - ceil(log2(8 n M))
+}
+
+__device__ __forceinline__ float det_scale_of(int32_t e) { return __builtin_ldexpf(1.0f, e); }   // 19 <= e <= 83 for fp16 inputs and n < 2^32
+
+// one term: the fp32 product, times 2^e, to the nearest integer
+__device__ __forceinline__ unsigned long long det_term(float prod, float scale)
+{
+  return (unsigned long long)(long long)__builtin_rintf(prod * scale);
+}
+
+// The plain and the persistent form.  lane = (sample, x bit, feature): the x-neighbour pair of one feature row is adjacent, so one wave instruction
+// carries an entry pair of 2 F 8-byte elements: one 64-byte request for F <= 4, two for F = 8 (grid_backward_plan).
+template <int F>
+__device__ __forceinline__ void grid_backward_det_lane(const GridDevice& grid, const float* __restrict__ coords, const half_t* __restrict__ dfeat,
+                                                       uint32_t in_width, unsigned long long* __restrict__ image, uint32_t level, uint32_t i, uint32_t r, float scale)
+{
+  const uint32_t xb = r / (uint32_t)F, f = r % (uint32_t)F;
+  const float g = (float)dfeat[(size_t)i * in_width + level * F + f];
+  if (g == 0.0f) return;
+  const bool nearest = grid.interpolation == 2u;
+  if (nearest && xb) return;
+  const LevelInfo lv = grid.levels[level];
+  const CornerSetup c = level_setup(lv, grid.interpolation == 1u ? 1u : 0u, coords[3 * (size_t)i], coords[3 * (size_t)i + 1], coords[3 * (size_t)i + 2]);
+  unsigned long long* base = image + (size_t)lv.offset * F + f;
+#pragma unroll
+  for (int yz = 0; yz < 4; ++yz) {
+    if (nearest && yz) break;
+    const int corner = (int)xb | (yz << 1);
+    const uint32_t idx = level_index(lv, c.g[0] + xb, c.g[1] + (uint32_t)(yz & 1), c.g[2] + (uint32_t)(yz >> 1));
+    const float w = nearest ? 1.0f : corner_weight(c, corner);
+    atomicAdd(base + (size_t)idx * F, det_term(w * g, scale));
+  }
+}
+
+template <int F>
+__global__ void __launch_bounds__(256) grid_backward_det_kernel(const GridDevice grid, const float* __restrict__ coords, const half_t* __restrict__ dfeat,
+                                                                uint32_t n, uint32_t in_width, unsigned long long* __restrict__ image, uint32_t level0,
+                                                                const DetScale* __restrict__ det)
+{
+  const int32_t e = det->e;
+  if (e == kDetNothing || e == kDetNonFinite) return;
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t i = t / (2u * F), r = t % (2u * F);
+  if (i >= n) return;
+  grid_backward_det_lane<F>(grid, coords, dfeat, in_width, image, level0 + blockIdx.y, i, r, det_scale_of(e));
+}
+
+template <int F>
+__global__ void __launch_bounds__(256) grid_backward_det_persistent_kernel(const GridDevice grid, const float* __restrict__ coords, const half_t* __restrict__ dfeat,
+                                                                           uint32_t n, uint32_t in_width, unsigned long long* __restrict__ image, uint32_t level0,
+                                                                           uint32_t n_levels, const DetScale* __restrict__ det)
+{
+  const int32_t e = det->e;
+  if (e == kDetNothing || e == kDetNonFinite) return;
+  const float scale = det_scale_of(e);
+  const uint32_t per_level = (n * 2u * F + 255u) & ~255u;
+  const uint64_t total = (uint64_t)per_level * n_levels;
+  for (uint64_t w = (uint64_t)blockIdx.x * 256u + threadIdx.x; w < total; w += (uint64_t)gridDim.x * 256u) {
+    const uint32_t level = level0 + (uint32_t)(w / per_level);
+    const uint32_t t = (uint32_t)(w % per_level);
+    const uint32_t i = t / (2u * F), r = t % (2u * F);
+    if (i >= n) continue;
+    grid_backward_det_lane<F>(grid, coords, dfeat, in_width, image, level, i, r, scale);
+  }
+}
+
+// The dense coarse levels: grid_backward_lds_kernel's tiles and slices with 64-bit LDS integer atomics (the tile holds 24 KB / (8 F) entries:
+// the same LDS per block as the production tiles, so the same number of blocks per CU), flushed with one 64-bit global atomic per entry element
+// that received something; contiguous elements, 8 per 64-byte request.
+template <int F>
+__global__ void __launch_bounds__(256) grid_backward_lds_det_kernel(const GridDevice grid, const LdsBwdItem* __restrict__ items, const float* __restrict__ coords,
+                                                                    const half_t* __restrict__ dfeat, uint32_t in_width, unsigned long long* __restrict__ image,
+                                                                    const DetScale* __restrict__ det)
+{
+  extern __shared__ unsigned long long s_acc64[];   // [e1 - e0][F]
+  const int32_t e = det->e;
+  if (e == kDetNothing || e == kDetNonFinite) return;
+  const float scale = det_scale_of(e);
+  const LdsBwdItem it = items[blockIdx.x];
+  const LevelInfo lv = grid.levels[it.level];
+  const uint32_t n_acc = (it.e1 - it.e0) * (uint32_t)F;
+  for (uint32_t q = threadIdx.x; q < n_acc; q += blockDim.x) s_acc64[q] = 0ull;
+  __syncthreads();
+  const bool nearest = grid.interpolation == 2u;
+  const uint32_t res2 = lv.resolution * lv.resolution;
+  for (uint32_t i = it.s0 + threadIdx.x; i < it.s1; i += blockDim.x) {
+    const float cx = coords[3 * (size_t)i], cy = coords[3 * (size_t)i + 1], cz = coords[3 * (size_t)i + 2];
+    {   // (the early drop of grid_backward_lds_kernel)
+      const uint32_t gx = (uint32_t)(int32_t)__builtin_floorf(__builtin_fmaf(cx, lv.scale, 0.5f));
+      const uint32_t gy = (uint32_t)(int32_t)__builtin_floorf(__builtin_fmaf(cy, lv.scale, 0.5f));
+      const uint32_t gz = (uint32_t)(int32_t)__builtin_floorf(__builtin_fmaf(cz, lv.scale, 0.5f));
+      const uint64_t lo = (uint64_t)gz * res2, hi = ((uint64_t)gz + 2u) * res2 + lv.resolution;
+      const bool in_domain = gx < lv.resolution && gy < lv.resolution && gz < lv.resolution;
+      if (in_domain && hi < lv.size && (hi < it.e0 || lo >= it.e1)) continue;
+    }
+    float g[F];
+    bool any = false;
+#pragma unroll
+    for (int f = 0; f < F; ++f) { g[f] = (float)dfeat[(size_t)i * in_width + it.level * F + f]; any = any || g[f] != 0.0f; }
+    if (!any) continue;
+    const CornerSetup c = level_setup(lv, grid.interpolation == 1u ? 1u : 0u, cx, cy, cz);
+#pragma unroll
+    for (int corner = 0; corner < 8; ++corner) {
+      if (nearest && corner) break;
+      const uint32_t idx = level_index(lv, c.g[0] + (corner & 1), c.g[1] + ((corner >> 1) & 1), c.g[2] + ((corner >> 2) & 1));
+      if (idx < it.e0 || idx >= it.e1) continue;
+      const float w = nearest ? 1.0f : corner_weight(c, corner);
+#pragma unroll
+      for (int f = 0; f < F; ++f)
+        if (g[f] != 0.0f) atomicAdd(&s_acc64[(idx - it.e0) * F + f], det_term(w * g[f], scale));
+    }
+  }
+  __syncthreads();
+  unsigned long long* base = image + ((size_t)lv.offset + it.e0) * F;
+  for (uint32_t q = threadIdx.x; q < n_acc; q += blockDim.x) {
+    const unsigned long long a = s_acc64[q];
+    if (a != 0ull) atomicAdd(base + q, a);
+  }
+}
+
+// int64 image [lo, hi) -> the fp16 blob: blob[i] = half(float(blob[i]) + sum[i] 2^-e), from double; what it consumed is cleared for the next
+// scatter, and it ADDS (fold_grid_grads_f32_kernel's contract: micro-batches accumulate).  A non-finite M writes NaN over the whole range.
+__global__ void fold_grid_grads_det_kernel(long long* __restrict__ image, half_t* __restrict__ grid_grads, size_t lo, size_t hi,
+                                           const DetScale* __restrict__ det)
+{
+  const int32_t e = det->e;
+  if (e == kDetNothing) return;
+  for (size_t i = lo + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < hi; i += (size_t)gridDim.x * blockDim.x) {
+    if (e == kDetNonFinite) { grid_grads[i] = (half_t)__builtin_nanf(""); continue; }
+    const long long v = image[i];
+    if (v == 0) continue;
+    image[i] = 0;
+    grid_grads[i] = (half_t)((double)(float)grid_grads[i] + __builtin_ldexp((double)v, -e));
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ Adam
 // EXTERNAL tcnn adam_step (optimizers/adam.h): see header comment.  Parameters [lo, hi); also clears the gradient for the next step.
 // Measured split at C4 (70 M parameters, tools/adam_probe.py, with the fp32 gradient blob of round 1): the sweep over all gradients
@@ -838,7 +1029,16 @@ struct TrainScratch {  // per-Network extra buffers that do not need to live in 
   DeviceBuffer<double> distance_partials{MemTag::Network};   // gradient_distance (diagnostics)
   DeviceBuffer<float> grid_grads_f32{MemTag::Network};       // n_features = 1: float image of the grid gradients (zero between steps)
   hipEvent_t fold_ev = nullptr;                              // ... and the join of its two scatter streams in front of the fold
-  ~TrainScratch() { if (fold_ev) (void)hipEventDestroy(fold_ev); }
+  // deterministic mode: int64 image of the grid part, 8 bytes per grid parameter (0.56 GB for the C4 model's 70 M), allocated by the first
+  // deterministic step and zero between steps; the exponent of the call; the LDS scatter's stream waits for it on scale_ev
+  DeviceBuffer<long long> grid_grads_i64{MemTag::Network};
+  DeviceBuffer<DetScale> det_scale{MemTag::Network};
+  hipEvent_t scale_ev = nullptr;
+  ~TrainScratch()
+  {
+    if (fold_ev) (void)hipEventDestroy(fold_ev);
+    if (scale_ev) (void)hipEventDestroy(scale_ev);
+  }
 };
 
 }  // namespace vnr
@@ -875,6 +1075,12 @@ static TrainScratch& scratch_of(const Network* n)
 }
 void network_release_scratch(const Network* n) { scratch_map().erase(n); }
 
+bool Network::deterministic_default()
+{
+  const char* e = std::getenv("VNR_AMD_DETERMINISTIC");
+  return e && std::atoi(e) != 0;
+}
+
 void Network::ensure_training_state(hipStream_t s)
 {
   if (opt_state_.count != n_params_) { opt_state_.resize(n_params_); launch_master_from_f16(params_f16_.ptr, opt_state_.ptr, n_params_, true, s); }
@@ -898,15 +1104,18 @@ GridBackwardPlan Network::grid_backward_plan(size_t batch) const
   constexpr uint32_t kLdsKb = 24, kLdsBlocks = 768, kLdsMaxTiles = 64;
   GridBackwardPlan p{};
   const uint32_t F = cfg_.n_features;
-  p.tile_entries = (kLdsKb * 1024u / (4u * F)) & ~15u;
+  // the deterministic form accumulates 8-byte integers, in tiles of the same 24 KB (grid_backward_lds_det_kernel)
+  const uint32_t acc_bytes = deterministic_ ? 8u : 4u;
+  p.tile_entries = (kLdsKb * 1024u / (acc_bytes * F)) & ~15u;
   p.lds_blocks = kLdsBlocks;
   p.n_levels = n_active_levels();
-  while (p.lds_levels < p.n_levels && !grid_.levels[p.lds_levels].hashed && ((size_t)grid_.levels[p.lds_levels].offset * F) % 2 == 0 &&
-         div_round_up(grid_.levels[p.lds_levels].size, p.tile_entries) <= kLdsMaxTiles) ++p.lds_levels;   // (the flush adds aligned pairs of halves)
+  while (p.lds_levels < p.n_levels && !grid_.levels[p.lds_levels].hashed && (deterministic_ || ((size_t)grid_.levels[p.lds_levels].offset * F) % 2 == 0) &&
+         div_round_up(grid_.levels[p.lds_levels].size, p.tile_entries) <= kLdsMaxTiles) ++p.lds_levels;   // (the fp16 flush adds aligned pairs of halves)
   // memory-side requests of one step (MI355X_MICROARCH.md "Global float atomics": a wave instruction leaves L2 as 64-byte requests).  The atomic
   // kernel's lanes are (sample, x bit, feature pair) with the two x-neighbours of a corner pair adjacent: ONE request per (sample, level, yz corner)
   // while an entry pair fits 64 bytes; an LDS tile flushes at most (entries x F x element bytes) / 64 requests per slice of the batch.
-  const uint32_t elem = F == 1 ? 4u : 2u;   // F = 1 scatters fp32 (network_train.hip GridGrad)
+  // (The deterministic kernel's lanes are (sample, x bit, feature) over 8-byte elements: the same count for F <= 4, twice it for F = 8.)
+  const uint32_t elem = deterministic_ ? 8u : F == 1 ? 4u : 2u;   // F = 1 scatters fp32 (network_train.hip GridGrad)
   p.atomic_requests = (uint64_t)batch * 4u * (p.n_levels - p.lds_levels) * std::max(1u, (2u * F * elem + 63u) / 64u);
   for (uint32_t l = 0; l < p.lds_levels; ++l) {
     const uint32_t tiles = div_round_up(grid_.levels[l].size, p.tile_entries);
@@ -930,16 +1139,41 @@ void Network::scatter_grid_gradients(const float* d_coords, size_t batch, hipStr
   const uint32_t tile_entries = plan.tile_entries, lds_levels = plan.lds_levels, lds_blocks = plan.lds_blocks;
   // n_features = 1: the scatter's target is the float image (fold_grid_grads_f32_kernel); the fold of a level range follows its scatter on the
   // same stream(s), before anybody (optimizer, exchange) reads the blob
+  // Deterministic mode (every F): the target of every form is the int64 image, folded the same way; the exponent of the call is computed
+  // first, on `s`, from all active levels' dL/dfeatures (a side stream's LDS scatter waits for it)
+  const bool det = deterministic_;
+  const half_t* dfeat = (const half_t*)ws_dfeat_.ptr;
   float* gg32 = nullptr;
-  if (cfg_.n_features == 1) {
+  if (cfg_.n_features == 1 && !det) {
     const size_t n_grid = grads_alloc() - n_mlp_;
     if (ts.grid_grads_f32.count != n_grid) { ts.grid_grads_f32.resize(n_grid); ts.grid_grads_f32.zero(s); VNR_HIP_CHECK(hipStreamSynchronize(s)); }
     gg32 = ts.grid_grads_f32.ptr;
   }
+  long long* gg64 = nullptr;
+  DetScale* d_det = nullptr;
+  if (det && n_active_levels() > 0) {
+    const size_t n_grid = grads_alloc() - n_mlp_;
+    if (ts.grid_grads_i64.count != n_grid) { ts.grid_grads_i64.resize(n_grid); ts.grid_grads_i64.zero(s); VNR_HIP_CHECK(hipStreamSynchronize(s)); }
+    ts.det_scale.ensure(1);
+    gg64 = ts.grid_grads_i64.ptr;
+    d_det = ts.det_scale.ptr;
+    VNR_HIP_CHECK(hipMemsetAsync(d_det, 0, sizeof(DetScale), s));
+    const uint64_t segs = (uint64_t)batch * (in_width_ / 8u);
+    grid_grad_scale_kernel<<<std::min<uint32_t>(div_round_up(segs, 256), Runtime::get().n_cus), 256, 0, s>>>(dfeat, n, in_width_,
+                                                                                                                  n_active_levels() * cfg_.n_features, d_det);
+    grid_grad_exponent_kernel<<<1, 1, 0, s>>>(d_det, n);
+    if (side_by_side) {
+      if (!ts.scale_ev) VNR_HIP_CHECK(hipEventCreateWithFlags(&ts.scale_ev, hipEventDisableTiming));
+      VNR_HIP_CHECK(hipEventRecord(ts.scale_ev, s));
+      VNR_HIP_CHECK(hipStreamWaitEvent(s_lds, ts.scale_ev, 0));
+    }
+  }
   auto fold = [&](uint32_t l0, uint32_t l1) {
-    if (!gg32 || l0 >= l1) return;
+    if ((!gg32 && !gg64) || l0 >= l1) return;
     const size_t lo = level_range_lo(l0) - n_mlp_, hi = level_range_hi(l1) - n_mlp_;
-    fold_grid_grads_f32_kernel<<<(uint32_t)std::min<size_t>(div_round_up(hi - lo, 256), (size_t)Runtime::get().n_cus * 16), 256, 0, s>>>(gg32, (half_t*)grads_.ptr + n_mlp_, lo, hi);
+    const uint32_t blocks = (uint32_t)std::min<size_t>(div_round_up(hi - lo, 256), (size_t)Runtime::get().n_cus * 16);
+    if (gg64) fold_grid_grads_det_kernel<<<blocks, 256, 0, s>>>(gg64, (half_t*)grads_.ptr + n_mlp_, lo, hi, d_det);
+    else fold_grid_grads_f32_kernel<<<blocks, 256, 0, s>>>(gg32, (half_t*)grads_.ptr + n_mlp_, lo, hi);
   };
   auto grid_backward_lds = [&](uint32_t l0, uint32_t l1) {
     // work items: every tile of every level x slices of the batch; more slices where a level has few tiles, so that ~2 blocks per CU exist
@@ -964,6 +1198,20 @@ void Network::scatter_grid_gradients(const float* d_coords, size_t batch, hipStr
       VNR_HIP_CHECK(hipStreamSynchronize(s_lds));   // pageable source
       ts.lds_items_host.assign((const uint8_t*)items.data(), (const uint8_t*)items.data() + item_bytes);
     }
+    if (gg64) {
+      const size_t shmem = (size_t)tile_entries * cfg_.n_features * sizeof(long long);
+      auto launch_det = [&](auto kernel) {
+        if (first_use_of_kernel((const void*)kernel)) VNR_HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        kernel<<<(uint32_t)items.size(), 256, shmem, s_lds>>>(grid_, (const LdsBwdItem*)ts.lds_items.ptr, d_coords, dfeat, in_width_, (unsigned long long*)gg64, d_det);
+      };
+      switch (cfg_.n_features) {
+      case 1: launch_det(grid_backward_lds_det_kernel<1>); break;
+      case 2: launch_det(grid_backward_lds_det_kernel<2>); break;
+      case 4: launch_det(grid_backward_lds_det_kernel<4>); break;
+      default: launch_det(grid_backward_lds_det_kernel<8>); break;
+      }
+      return;
+    }
     const size_t shmem = (size_t)tile_entries * cfg_.n_features * sizeof(float);
     half_t* gg = (half_t*)grads_.ptr + n_mlp_;
     auto launch = [&](auto kernel, auto* out) {
@@ -983,11 +1231,32 @@ void Network::scatter_grid_gradients(const float* d_coords, size_t batch, hipStr
       l0 = std::min(l1, lds_levels);
       if (l0 >= l1) return;
     }
+    constexpr uint32_t kBlocksPerCu = 2;   // persistent form (swept 2 / 3 / 4 / 6 / 8, profiles/r05_train_overlap_ab.txt)
+    if (gg64) {   // one lane per (sample, x bit, feature)
+      unsigned long long* img = (unsigned long long*)gg64;
+      const dim3 gd(div_round_up((uint64_t)batch * 2u * cfg_.n_features, 256), l1 - l0);
+      if (side_by_side) {
+        const uint32_t blocks = std::min<uint32_t>(gd.x * gd.y, (uint32_t)Runtime::get().n_cus * kBlocksPerCu);
+        switch (cfg_.n_features) {
+        case 1: grid_backward_det_persistent_kernel<1><<<blocks, 256, 0, s>>>(grid_, d_coords, dfeat, n, in_width_, img, l0, l1 - l0, d_det); break;
+        case 2: grid_backward_det_persistent_kernel<2><<<blocks, 256, 0, s>>>(grid_, d_coords, dfeat, n, in_width_, img, l0, l1 - l0, d_det); break;
+        case 4: grid_backward_det_persistent_kernel<4><<<blocks, 256, 0, s>>>(grid_, d_coords, dfeat, n, in_width_, img, l0, l1 - l0, d_det); break;
+        default: grid_backward_det_persistent_kernel<8><<<blocks, 256, 0, s>>>(grid_, d_coords, dfeat, n, in_width_, img, l0, l1 - l0, d_det); break;
+        }
+        return;
+      }
+      switch (cfg_.n_features) {
+      case 1: grid_backward_det_kernel<1><<<gd, 256, 0, s>>>(grid_, d_coords, dfeat, n, in_width_, img, l0, d_det); break;
+      case 2: grid_backward_det_kernel<2><<<gd, 256, 0, s>>>(grid_, d_coords, dfeat, n, in_width_, img, l0, d_det); break;
+      case 4: grid_backward_det_kernel<4><<<gd, 256, 0, s>>>(grid_, d_coords, dfeat, n, in_width_, img, l0, d_det); break;
+      default: grid_backward_det_kernel<8><<<gd, 256, 0, s>>>(grid_, d_coords, dfeat, n, in_width_, img, l0, d_det); break;
+      }
+      return;
+    }
     const uint32_t pairs = cfg_.n_features >= 2 ? cfg_.n_features / 2 : 1u;
     const dim3 g(div_round_up((uint64_t)batch * pairs * 2, 256), l1 - l0);  // one lane per (sample, x bit, feature pair)
     half_t* gg = (half_t*)grads_.ptr + n_mlp_;
     if (side_by_side) {   // a few blocks per CU walk the same lanes
-      constexpr uint32_t kBlocksPerCu = 2;   // (swept 2 / 3 / 4 / 6 / 8, profiles/r05_train_overlap_ab.txt)
       const uint32_t blocks = std::min<uint32_t>(g.x * g.y, (uint32_t)Runtime::get().n_cus * kBlocksPerCu);
       switch (cfg_.n_features) {
       case 1: grid_backward_persistent_kernel<1><<<blocks, 256, 0, s>>>(grid_, d_coords, (const half_t*)ws_dfeat_.ptr, n, in_width_, gg32, l0, l1 - l0); break;
@@ -1020,7 +1289,7 @@ void Network::scatter_grid_gradients(const float* d_coords, size_t batch, hipStr
     // levels at or beyond max_level + 1e-3 encode to zero and receive no gradient (EXTERNAL tcnn kernel_grid_backward has the same test)
     if (only.first >= 0) grid_backward((uint32_t)only.first, std::min<uint32_t>((uint32_t)only.second, n_active_levels()));
     else if (n_active_levels() > 0) grid_backward(0, n_active_levels());
-    if (gg32 && n_active_levels() > 0) {
+    if ((gg32 || gg64) && n_active_levels() > 0) {
       if (side_by_side) {   // the dense levels' LDS scatter runs on s_lds and is joined by the caller only later: the fold waits for it here
         if (!ts.fold_ev) VNR_HIP_CHECK(hipEventCreateWithFlags(&ts.fold_ev, hipEventDisableTiming));
         VNR_HIP_CHECK(hipEventRecord(ts.fold_ev, s_lds));
@@ -1231,7 +1500,12 @@ const void* Network::training_buffer(int which, size_t* bytes) const
   case 1: *bytes = ws_dfeat_.bytes(); return ws_dfeat_.ptr;
   case 2: *bytes = ws_features_.bytes(); return ws_features_.ptr;
   case 3: *bytes = ws_acts_.bytes(); return ws_acts_.ptr;
-  default: throw std::runtime_error("training_buffer: 0 gradients, 1 dL/dfeatures, 2 features, 3 activations");
+  case 4: {   // the deterministic mode's int64 image of the grid part (zero between steps; absent before the first deterministic step)
+    const TrainScratch& ts = scratch_of(this);
+    *bytes = ts.grid_grads_i64.bytes();
+    return ts.grid_grads_i64.ptr;
+  }
+  default: throw std::runtime_error("training_buffer: 0 gradients, 1 dL/dfeatures, 2 features, 3 activations, 4 the deterministic int64 image");
   }
 }
 

@@ -9,6 +9,7 @@
   --training-mode / --mode   the data sampling mode: GPU | OUT_OF_CORE | NOTHING                [GPU]
   --quiet                    quiet mode
   --train-macrocell          train the macrocell grid at the same time
+  --deterministic            bit-reproducible training (new: vnrAmdNeuralVolumeSetDeterministicTraining; not over RCCL)
 
 Like the reference it trains in bursts of 10 steps in fast mode, restarts when the loss is still > 0.9 after 5000 steps, prints
 the Summary block (STEP / LOSS / TIME / PSNR / SSIM) and writes ./params.json (BSON).
@@ -36,6 +37,8 @@ def main(argv=None):
     p.add_argument("--training-mode", "--mode", dest="training_mode", default="GPU", metavar="string", help="the data sampling mode")
     p.add_argument("--quiet", action="store_true", help="quiet mode")
     p.add_argument("--train-macrocell", action="store_true", help="train the macrocell grid at the same time")
+    p.add_argument("--deterministic", action="store_true",
+                   help="bit-reproducible training: the hash-grid gradient is summed in 64-bit fixed point (slower; not over RCCL)")
     a = p.parse_args(argv)
 
     ctx = dist.init_from_env()        # one rank: binds the GPU; more: meets the other ranks (RCCL)
@@ -46,6 +49,8 @@ def main(argv=None):
         neural_volume = api.vnrCreateNeuralVolume(a.network, simple_volume, bool(a.train_macrocell))
         if a.resume:
             api.vnrNeuralVolumeSetParams(neural_volume, a.resume)
+        if a.deterministic:
+            api.neural_set_deterministic_training(neural_volume, True)
         report = None
         if root and a.report not in ("", "none"):
             report = open(a.report if a.report.endswith(".csv") else a.report + ".csv", "w")

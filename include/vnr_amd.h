@@ -141,6 +141,46 @@ vnrAmdVolume vnrAmdCreateSimpleVolumeOutOfCore(const char* filename, const int d
 vnrAmdVolume vnrAmdCreateSimpleVolumeFromScene(const void* scene, size_t size, int format, const char* mode, int save_loaded_volume);
 int  vnrAmdSimpleVolumeGetNumberOfTimeSteps(vnrAmdVolume);            /* vnrSimpleVolumeGetNumberOfTimeSteps (api.h:119) */
 int  vnrAmdSimpleVolumeSetCurrentTimeStep(vnrAmdVolume, int index);   /* vnrSimpleVolumeSetCurrentTimeStep (api.h:118) */
+/* AMD extension: in-situ ground truth.  The voxels are in device memory already (a simulation's output, another kernel's result,
+ * the next step of a time series): they are normalised on the GPU with the arithmetic of the host path, so the volume equals
+ * vnrAmdCreateSimpleVolumeFromMemory of the same array bit for bit (voxels, data range, macrocell).
+ *   d_data      typed voxels, x fastest, aligned to the value type: VNR_AMD_TYPE_UINT8 / INT8 / UINT16 / INT16 / UINT32 / INT32 /
+ *               FLOAT / DOUBLE.  The 64-bit integer and the vector types are refused.  It is a pointer of the HIP runtime the
+ *               library runs on: vnrAmdMalloc, or the application's own hipMalloc against the same libamdhip64.  A PyTorch tensor
+ *               is not one: the PyTorch wheel's bundled second ROCm runtime cannot share the device with the library's
+ *               (INTEGRATION.md §4), unless torch was imported first and the library bound to torch's runtime.
+ *   strides     three element strides (sx, sy, sz), all positive, for a field with ghost layers or a sub-box of a larger array
+ *               (d_data points at the first voxel of the box); NULL = dense.  sx == 1 is read 16 bytes per lane, any other sx
+ *               voxel by voxel.
+ *   range       range_lo > range_hi = min / max of the data (the source is then read twice, otherwise once); used_range (may be
+ *               NULL) receives the range that was applied.
+ *   stream      the hipStream_t the caller produced d_data on; NULL = the data is complete.  The library records an event on it and
+ *               makes its own stream wait for that event; the caller's stream is never blocked or synchronised.
+ * Every call returns after the ingest and the macrocell pass have completed, like the other load paths: on return the caller may
+ * overwrite or free d_data.  The volume never keeps a pointer to d_data, and d_data must not overlap the volume's own voxels.
+ * Errors (NULL / VNR_AMD_ERROR / -1 and a message): null data, non-positive dims, a stride <= 0, a refused value type, an
+ * out-of-core or "NOTHING" volume, a neural volume, a volume whose dims are not the ones it was created with, no usable device.
+ * A refused call leaves the volume as it was.
+ *
+ * Create: as vnrAmdCreateSimpleVolumeFromMemory (dims, transform, clip box, macrocell, data range).
+ * Update: replaces the voxels of the current time step in place: same dims, vnrAmdSimpleVolumeDeviceData keeps its value.  Then
+ *   the volume's macrocell is rebuilt from the new voxels alone -- it equals a fresh volume's; vnrAmdSimpleVolumeSetCurrentTimeStep
+ *   only widens the cells by the step it switches to -- and, if a transfer function is set, its max opacity.  The data range becomes the new step's on a one-step volume and is extended by it otherwise.  A neural volume created
+ *   on this volume goes on training from the new voxels with its current parameters and optimizer state (a warm start).  Its own
+ *   online macrocell is NOT reset, exactly as at a time-step switch: it still bounds the earlier data as well, which is
+ *   conservative where values left a cell and keeps tightening only through training samples; a neural volume that shares the
+ *   ground truth's macrocell (online_macrocell_construction = 0) sees the recomputed one at once.  A renderer with pipelined or
+ *   asynchronous frames in flight (vnrAmdRendererRenderPipelined, vnrAmdRendererSetAsync) must be flushed before the call, as
+ *   before a time-step switch: frames in flight read the voxels that are being replaced.
+ * Append: adds a time step (vnrAmdSimpleVolumeGetNumberOfTimeSteps / ...SetCurrentTimeStep then work on volumes built without
+ *   scene files); the current step stays current; the data range is extended as by a scene's further steps.  Returns the new
+ *   step's index, -1 on error. */
+vnrAmdVolume vnrAmdCreateSimpleVolumeFromDevice(const void* d_data, const int dims[3], int value_type, const int64_t strides[3],
+                                                float range_lo, float range_hi, void* stream, float used_range[2]);
+int  vnrAmdSimpleVolumeUpdateFromDevice(vnrAmdVolume, const void* d_data, int value_type, const int64_t strides[3],
+                                        float range_lo, float range_hi, void* stream, float used_range[2]);
+int  vnrAmdSimpleVolumeAppendTimeStepFromDevice(vnrAmdVolume, const void* d_data, int value_type, const int64_t strides[3],
+                                                float range_lo, float range_hi, void* stream, float used_range[2]);
 /* the value range a scene maps its transfer function to (view.volume.scalarMappingRange[Unnormalized], serializer.cpp:212-256);
  * returns 2 and leaves `range` untouched when the scene has none (VNR_AMD_OK when it has, VNR_AMD_ERROR on a malformed scene) */
 int  vnrAmdSceneGetValueRange(const void* scene, size_t size, int format, float range[2]);

@@ -227,6 +227,10 @@ def lib():
     sig("vnrAmdSimpleVolumeSample", I, P, SZ, P, P, I, P)
     sig("vnrAmdNeuralVolumeUpdateMacrocell", I, P, SZ, P, P, P)
     sig("vnrAmdVolumeUpdateMaxOpacity", I, P, P)
+    I64P = C.POINTER(C.c_int64)
+    sig("vnrAmdCreateSimpleVolumeFromDevice", P, P, IP, I, I64P, F, F, P, FP)
+    sig("vnrAmdSimpleVolumeUpdateFromDevice", I, P, P, I, I64P, F, F, P, FP)
+    sig("vnrAmdSimpleVolumeAppendTimeStepFromDevice", I, P, P, I, I64P, F, F, P, FP)
     _lib = L
     return L
 

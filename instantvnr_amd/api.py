@@ -244,6 +244,62 @@ def vnrSimpleVolumeSetCurrentTimeStep(v, index):
     check(lib().vnrAmdSimpleVolumeSetCurrentTimeStep(v.h, int(index)))
 
 
+def _device_source_args(d_ptr, dtype, strides, value_range, stream, dims=None):
+    """checks and packs the arguments the three FromDevice calls share; raises before the library is called"""
+    try:
+        dt = np.dtype(dtype)
+    except TypeError:
+        raise VnrAmdError(f"unknown data type {dtype!r}") from None
+    if dt not in VALUE_TYPES:
+        raise VnrAmdError(f"unknown data type {dt}: device data is one of {sorted(str(k) for k in VALUE_TYPES)}")
+    ptr = d_ptr.ptr if isinstance(d_ptr, DeviceArray) else d_ptr
+    if not ptr:
+        raise VnrAmdError("null device data")
+    d = None
+    if dims is not None:
+        dl = [int(v) for v in np.atleast_1d(dims)]
+        if len(dl) != 3 or min(dl) <= 0:
+            raise VnrAmdError(f"dims must be three positive sizes (x, y, z), got {dims!r}")
+        d = (C.c_int * 3)(*dl)
+    s = None
+    if strides is not None:
+        sl = [int(v) for v in np.atleast_1d(strides)]
+        if len(sl) != 3 or min(sl) <= 0:
+            raise VnrAmdError(f"strides must be three positive element strides (sx, sy, sz), got {strides!r}")
+        s = (C.c_int64 * 3)(*sl)
+    lo, hi = (1.0, 0.0) if value_range is None else value_range
+    return C.c_void_p(ptr), d, VALUE_TYPES[dt], s, float(lo), float(hi), C.c_void_p(stream) if stream else None
+
+
+def vnrCreateSimpleVolumeFromDevice(d_ptr, dims, dtype, strides=None, value_range=None, stream=None):
+    """AMD extension (include/vnr_amd.h, "in-situ ground truth"): a simple volume from typed voxels in device memory.  `d_ptr` is a
+    DeviceArray or a raw device address of the runtime the library runs on, dims = (x, y, z), strides in elements or None for a
+    dense array, value_range None = min / max of the data, stream = the hipStream_t the data was produced on.
+    -> (volume, (lo, hi) that was applied)"""
+    p, d, t, s, lo, hi, st = _device_source_args(d_ptr, dtype, strides, value_range, stream, dims)
+    used = np.zeros(2, np.float32)
+    v = vnrVolume(lib().vnrAmdCreateSimpleVolumeFromDevice(p, d, t, s, lo, hi, st, _fp(used)))
+    return v, (float(used[0]), float(used[1]))
+
+
+def vnrSimpleVolumeUpdateFromDevice(v, d_ptr, dtype, strides=None, value_range=None, stream=None):
+    """replaces the voxels of the current time step in place (same dims) -> (volume, applied range)"""
+    p, _, t, s, lo, hi, st = _device_source_args(d_ptr, dtype, strides, value_range, stream)
+    used = np.zeros(2, np.float32)
+    check(lib().vnrAmdSimpleVolumeUpdateFromDevice(v.h, p, t, s, lo, hi, st, _fp(used)))
+    return v, (float(used[0]), float(used[1]))
+
+
+def vnrSimpleVolumeAppendTimeStepFromDevice(v, d_ptr, dtype, strides=None, value_range=None, stream=None):
+    """adds a time step; the current one stays current -> (index of the new step, applied range)"""
+    p, _, t, s, lo, hi, st = _device_source_args(d_ptr, dtype, strides, value_range, stream)
+    used = np.zeros(2, np.float32)
+    index = lib().vnrAmdSimpleVolumeAppendTimeStepFromDevice(v.h, p, t, s, lo, hi, st, _fp(used))
+    if index < 0:
+        raise VnrAmdError(_lib.last_error())
+    return index, (float(used[0]), float(used[1]))
+
+
 def scene_value_range(scene):
     """the value range a scene maps its transfer function to, or None (serializer.cpp:212-256)"""
     b, n, f = _json_arg(scene)

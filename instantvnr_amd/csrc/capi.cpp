@@ -421,6 +421,34 @@ int vnrAmdSimpleVolumeOutOfCoreBlocks(vnrAmdVolume v, int* block_index_yz, size_
     for (size_t i = 0; i < b.size(); ++i) { block_index_yz[2 * i] = b[i].index_y; block_index_yz[2 * i + 1] = b[i].index_z; }
   });
 }
+vnrAmdVolume vnrAmdCreateSimpleVolumeFromDevice(const void* d_data, const int dims[3], int value_type, const int64_t strides[3],
+                                                float lo, float hi, void* stream, float used_range[2])
+{
+  return guarded_new<vnrAmdVolume_t>([&]() {
+    if (!dims) throw std::runtime_error("null dims");
+    auto sv = std::make_shared<SimpleVolume>();
+    sv->create_from_device(DeviceSource{d_data, value_type, strides, (hipStream_t)stream}, {dims[0], dims[1], dims[2]}, lo, hi, used_range);
+    auto* h = new vnrAmdVolume_t();
+    h->v = sv;
+    return h;
+  });
+}
+int vnrAmdSimpleVolumeUpdateFromDevice(vnrAmdVolume v, const void* d_data, int value_type, const int64_t strides[3], float lo, float hi,
+                                       void* stream, float used_range[2])
+{
+  return guarded([&]() {
+    as_simple(v)->update_from_device(DeviceSource{d_data, value_type, strides, (hipStream_t)stream}, lo, hi, used_range);
+  });
+}
+int vnrAmdSimpleVolumeAppendTimeStepFromDevice(vnrAmdVolume v, const void* d_data, int value_type, const int64_t strides[3], float lo,
+                                               float hi, void* stream, float used_range[2])
+{
+  int index = -1;
+  guarded([&]() {
+    index = as_simple(v)->append_from_device(DeviceSource{d_data, value_type, strides, (hipStream_t)stream}, lo, hi, used_range);
+  });
+  return index;
+}
 const float* vnrAmdSimpleVolumeDeviceData(vnrAmdVolume v)
 {
   const float* p = nullptr;

@@ -55,6 +55,7 @@ public:
   void set_spacings(vec3f s) { spacings_ = s; }
   void set_external(MacroCell* ext) { external_ = ext; }  // macrocell.cu:203-211
   void allocate(hipStream_t s);                          // macrocell.cu:213-219 (value ranges zero-initialised)
+  void reset_value_range(hipStream_t s) { target().value_range_.zero(s); }   // back to the state allocate() leaves: compute_everything only ever widens
   bool is_external() const { return external_ != nullptr; }
   bool allocated() const { return target().value_range_.count > 0; }
 
@@ -77,6 +78,15 @@ private:
   vec3f spacings_{1, 1, 1};
   DeviceBuffer<float> value_range_, max_opacity_;
   MacroCell* external_ = nullptr;
+};
+
+// Typed voxels in device memory (ingest.hip): x fastest; `strides` in elements, or null for a dense array.  `producer` is the
+// stream the data was written on (null: it is complete already); nothing of this is kept after the call that takes it.
+struct DeviceSource {
+  const void* data = nullptr;
+  int type = 8;
+  const int64_t* strides = nullptr;
+  hipStream_t producer = nullptr;
 };
 
 struct VolumeDesc {  // MultiVolume, instantvnr_types.h:40-56 (single timestep)
@@ -113,6 +123,14 @@ public:
                         uint64_t n_concurrent_blocks, uint64_t n_blocks);
   // vnrCreateSimpleVolume(scene, mode, save) (api.cpp:145-158): "GPU", "OUT_OF_CORE" or "NOTHING"; one file per time step
   void load_scene(const SceneVolume& scene, const std::string& mode, bool save_volume);
+  // In-situ ground truth (ingest.hip; no reference counterpart): the voxels are in device memory already.  Same result as
+  // load_host of the same array, bit for bit.  create = load_host + finish_load; update replaces the current time step in place
+  // (same dims, same device address), then the macrocell is rebuilt from the new voxels alone (a time-step switch only widens it)
+  // and the max opacity follows as in set_current_timestep; append adds a time step and returns its index, the current step
+  // stays current.  used_range (may be null) receives the range that was applied.
+  void create_from_device(const DeviceSource& src, vec3i dims, float range_lo, float range_hi, float used_range[2]);
+  void update_from_device(const DeviceSource& src, float range_lo, float range_hi, float used_range[2]);
+  int append_from_device(const DeviceSource& src, float range_lo, float range_hi, float used_range[2]);
   int num_timesteps() const { return steps_.empty() ? 1 : (int)steps_.size(); }   // SimpleVolume::get_num_timesteps
   void set_current_timestep(int index);                                           // core/sampler.cu:19-26
   bool has_data() const { return data_.ptr != nullptr; }   // SimpleVolume::texture() != 0
@@ -133,6 +151,10 @@ public:
 
 private:
   void finish_load(hipStream_t s);
+  void validate_device_source(const DeviceSource& src, vec3i dims) const;
+  void require_resident_for_ingest(const char* what) const;
+  void ingest_device(const DeviceSource& src, vec3i dims, float& lo, float& hi, float* dst, hipStream_t s);
+  DeviceBuffer<double> ingest_partials_;     // block partials of the min/max pass + its result
   DeviceBuffer<float> data_;                 // the current time step
   std::vector<DeviceBuffer<float>> steps_;   // the other time steps (entry `current_step_` is moved into data_)
   int current_step_ = 0;

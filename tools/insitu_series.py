@@ -1,0 +1,133 @@
+#!/usr/bin/env python3
+"""In-situ training of a time series: the example and the measuring tool of the device ingest (include/vnr_amd.h, "in-situ ground truth").
+
+A short seeded series (instantvnr_amd/synthetic.py: a vortex field, advected along x and fading from step to step) stands for a
+simulation whose output lives in device memory: every step is put into a vnrAmdMalloc buffer.  The volume is created from the first
+step (vnrAmdCreateSimpleVolumeFromDevice) and a neural volume on it; for every further step the voxels are replaced in place
+(vnrAmdSimpleVolumeUpdateFromDevice), the network trains --steps-per-frame steps from where it stands, and the step's PSNR and the
+ingest time are printed.
+
+  --size N               voxels per axis                                                      [64]
+  --dtype T              uint8 | int8 | uint16 | int16 | uint32 | int32 | float32 | float64     [uint8]
+  --frames K             time steps of the series                                              [4]
+  --steps-per-frame S    training steps per time step (0: ingest only)                         [100]
+  --ghost G              G ghost layers on every side of the source array (strided ingest)      [0]
+  --range-from-data      min / max of every step instead of the type's range (reads the source twice)
+  --repeat R             time every ingest R times, report the fastest and the median          [5]
+  --compare-host         also time vnrAmdCreateSimpleVolumeFromMemory on the same array (the path a host-resident field takes)
+  --seed N                                                                                     [1]
+
+Times are host clocks around calls that end in a device synchronise.  "update" is the whole vnrAmdSimpleVolumeUpdateFromDevice call
+(ingest kernels + macrocell pass); "macrocell" is the macrocell pass alone (vnrAmdSimpleVolumeSetCurrentTimeStep on the current step);
+"ingest" is their difference, and the GB/s are the bytes the ingest must move (source bytes once or twice + 4 bytes written per voxel)
+over it.  Kernel times proper: run this under rocprofv3 --kernel-trace --stats (the kernels are ingest_minmax_kernel,
+ingest_minmax_final_kernel, ingest_convert_kernel)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from instantvnr_amd import api, synthetic as syn  # noqa: E402
+
+FULL_SCALE = {"uint8": 255.0, "int8": 127.0, "uint16": 65535.0, "int16": 32767.0, "uint32": 4294967040.0, "int32": 2147483520.0,
+              "float32": 1.0, "float64": 1.0}
+
+
+def series(size, frames, dtype, seed):
+    """frames arrays [z, y, x] of `dtype`: a seeded vortex field moving along x and fading"""
+    b = min(size, 64)
+    base = syn.vortex_volume(b, seed=seed)
+    if size != b:
+        idx = np.arange(size) * b // size
+        base = base[np.ix_(idx, idx, idx)]
+    scale = np.float32(FULL_SCALE[np.dtype(dtype).name])
+    for t in range(frames):
+        f = np.roll(base, t * max(1, size // 16), axis=2) * np.float32(1.0 - 0.4 * t / max(1, frames))
+        yield np.ascontiguousarray((f * scale).astype(dtype))
+
+
+def with_ghost_layers(a, g):
+    """-> (padded array, element offset of the first voxel, strides) for g ghost layers per side"""
+    if g == 0:
+        return a, 0, None
+    p = np.zeros(tuple(s + 2 * g for s in a.shape), a.dtype)
+    p[g:-g, g:-g, g:-g] = a
+    sy, sz = p.shape[2], p.shape[2] * p.shape[1]
+    return p, g + g * sy + g * sz, (1, sy, sz)
+
+
+def timed(fn, repeat):
+    out, times = None, []
+    for _ in range(repeat):
+        t0 = time.perf_counter()
+        out = fn()
+        times.append((time.perf_counter() - t0) * 1e3)
+    return out, min(times), statistics.median(times)
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser(description="in-situ training of a time series from device memory")
+    p.add_argument("--size", type=int, default=64)
+    p.add_argument("--dtype", default="uint8", choices=sorted(FULL_SCALE))
+    p.add_argument("--frames", type=int, default=4)
+    p.add_argument("--steps-per-frame", type=int, default=100)
+    p.add_argument("--ghost", type=int, default=0)
+    p.add_argument("--range-from-data", action="store_true")
+    p.add_argument("--repeat", type=int, default=5)
+    p.add_argument("--compare-host", action="store_true")
+    p.add_argument("--seed", type=int, default=1)
+    a = p.parse_args(argv)
+
+    api._lib.require_device()
+    api.check(api.lib().vnrAmdInit(-1))
+    dtype = np.dtype(a.dtype)
+    dims = (a.size,) * 3
+    n = a.size ** 3
+    value_range = None if a.range_from_data else (0.0, FULL_SCALE[a.dtype])
+    passes = 2 if a.range_from_data else 1
+    bytes_read, bytes_written = passes * n * dtype.itemsize, 4 * n
+    print(f"library build {api.lib().vnrAmdBuildId().decode()}; {a.size}^3 {a.dtype}, ghost {a.ghost}, range "
+          f"{'from the data' if a.range_from_data else value_range}, ingest reads {bytes_read} B and writes {bytes_written} B")
+
+    volume = neural = None
+    for t, step in enumerate(series(a.size, a.frames, dtype, a.seed)):
+        source, offset, strides = with_ghost_layers(step, a.ghost)
+        d = api.DeviceArray.from_numpy(source)              # the "simulation output": typed voxels in device memory
+        ptr = d.ptr + offset * dtype.itemsize
+        row = {"step": t}
+        if volume is None:
+            (volume, used), row["create_ms"], _ = timed(lambda: api.vnrCreateSimpleVolumeFromDevice(ptr, dims, dtype, strides, value_range), 1)
+            if a.steps_per_frame:
+                neural = api.vnrCreateNeuralVolume(syn.model_config(n_levels=8, n_features=8, log2_hashmap_size=15, base_resolution=16), volume)
+        else:
+            (_, used), best, median = timed(lambda: api.vnrSimpleVolumeUpdateFromDevice(volume, ptr, dtype, strides, value_range), a.repeat)
+            _, mc_best, mc_median = timed(lambda: api.vnrSimpleVolumeSetCurrentTimeStep(volume, 0), a.repeat)
+            ingest = max(best - mc_best, 1e-6)
+            row.update(update_ms=round(best, 4), update_median_ms=round(median, 4), macrocell_ms=round(mc_best, 4),
+                       macrocell_median_ms=round(mc_median, 4), ingest_ms=round(ingest, 4),
+                       ingest_GBps=round((bytes_read + bytes_written) / ingest / 1e6, 1))
+        row["used_range"] = used
+        if a.compare_host:
+            host, row["host_create_ms"], row["host_create_median_ms"] = timed(lambda: api.vnrCreateSimpleVolume(step, value_range=value_range),
+                                                                               1 if t == 0 else min(a.repeat, 3))
+            host.release()
+        d.free()
+        if neural is not None:
+            t0 = time.perf_counter()
+            api.vnrNeuralVolumeTrain(neural, a.steps_per_frame, True)
+            row["train_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
+            row["psnr"] = round(api.vnrNeuralVolumeGetPSNR(neural), 3)
+        for k in ("create_ms", "host_create_ms", "host_create_median_ms"):
+            if k in row:
+                row[k] = round(row[k], 4)
+        print(json.dumps(row))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -239,6 +239,55 @@ int    vnrAmdNeuralVolumeSerializeParams(vnrAmdVolume, void** bson, size_t* size
 /* NeuralVolume::inference (core/network.cu:1043-1052): n coords [n][3] fp32 -> n fp32 values.
  * Buffers need not be padded (the reference pads n to 256 and reads/writes the pad). */
 int    vnrAmdNeuralVolumeInference(vnrAmdVolume, size_t n, const float* d_coords, float* d_values, void* stream);
+/* AMD extension: in-situ round trip, the other half of the in-situ ground truth above.  A trained neural volume is decoded into
+ * the application's own typed device array, and the error of exactly those voxels against a field in device memory is reported,
+ * both without a host round trip and without a full-size intermediate buffer.
+ *   grid_dims   the virtual voxel grid the box indexes; NULL = the volume's dims.  Any positive dims: a finer grid super-samples,
+ *               a coarser one is a preview.  (ErrorAgainstDevice always works on the volume's own grid.)
+ *   box         box_lo / box_size, a box inside that grid; NULL / NULL = the whole grid.  Voxel (i, j, k) of the box is the
+ *               network's value at ((float)(box_lo + ijk) + 0.5f) * (1.0f / (float)grid_dims) per axis, in fp32: the coordinates
+ *               vnrAmdNeuralVolumeDecodeProgressive uses.  A VNR_AMD_TYPE_FLOAT decode without a range therefore equals
+ *               vnrAmdNeuralVolumeInference at these coordinates bit for bit, and on the volume's own grid the decoded volume.
+ *   d_out/d_ref points at the first voxel of the box in the array; value types, alignment, runtime and `strides` (elements, all
+ *               positive, NULL = dense over box_size) as for d_data above.  Strides that would put two voxels of the box at one
+ *               address are refused: ordered by stride, each axis longer than one voxel must step at least over the extent of
+ *               the axes below it.  Where the runtime knows the allocation the pointer lies in, a box that does not fit is refused.
+ *   range       the conversion of the network's output v (which is NOT clamped to [0, 1] first) to the stored voxel, step by step:
+ *                 d = __fadd_rn(__fmul_rn(v, range_hi - range_lo), range_lo)   two fp32 roundings, never one fma; the width in fp32
+ *                 range_lo > range_hi: d = v (FLOAT / DOUBLE only; the integer types need a range); range_lo == range_hi is refused
+ *                 FLOAT stores d, DOUBLE (double)d, an integer type rint((double)d) (ties to even) saturated to the type's limits,
+ *                 a NaN as 0.
+ *               vnrAmdSimpleVolumeGetDataRange of the ground truth is the range that inverts the ingest.
+ *   stream      the hipStream_t of the caller that may still be reading d_out's previous content / that produced d_ref; NULL =
+ *               none.  The library records an event on it and makes its own stream wait; the caller's stream is never blocked or
+ *               synchronised.  Both calls return after their work has completed.
+ * The work runs in chunks of VNR_AMD_DECODE_CHUNK samples (read at every call; default 4194304, at most 2^28) through scratch the
+ * volume keeps: 16 bytes per sample of the largest chunk so far.  The result does not depend on the chunk size.  With sx == 1 the
+ * array is accessed 16 bytes per lane, cut at the 16-byte boundaries of its address, ragged row ends element by element; any
+ * other sx goes voxel by voxel.  Nothing but the box's voxels is written: ghost layers keep their bytes.  A dense FLOAT decode
+ * without a range is written by the evaluation kernel itself.
+ *
+ * ErrorAgainstDevice: per voxel e = (double)decoded - (double)ref, where decoded is the typed value DecodeToDevice would store for
+ * this value type and range (quantisation included).  n_voxels = voxels of the box; max_abs = max |e| and worst = the grid index
+ * of the voxel that has it (the lowest x-fastest index among equals), both exact; sum_abs, sum_sq = sums of |e| and e * e in
+ * double (their last bits depend on the chunk size); psnr_db = 10 log10((range_hi - range_lo)^2 * n_voxels / sum_sq), the range
+ * taken as 1 when none is given.  d_block_max (may be NULL): a float per macrocell, dims and order of vnrAmdVolumeGetMacrocell
+ * (16^3 voxels, x fastest): max |e| of the cell's voxels inside the box rounded to float, 0 where the box has none.
+ * NaN: the integer types never decode to one.  For FLOAT / DOUBLE a voxel where decoded or ref is a NaN makes sum_abs, sum_sq and
+ * psnr_db NaN -- that is how the caller learns of it -- while max_abs, worst and the block map are those of the other voxels
+ * (max_abs NaN and worst -1, -1, -1 if there is no other voxel).
+ *
+ * Errors (VNR_AMD_ERROR and a message; nothing has been written, the volume is as it was): a null pointer, a simple volume, a
+ * neural volume without a valid network, non-positive grid dims or box sizes, a box outside the grid, box_lo without box_size,
+ * a stride <= 0, overlapping strides, a refused value type, an integer type without a range, range_lo == range_hi, a pointer not
+ * aligned to its type, a box beyond its allocation, a malformed VNR_AMD_DECODE_CHUNK, no usable device. */
+typedef struct vnrAmdDecodeError { uint64_t n_voxels; double max_abs; int worst[3]; double sum_abs, sum_sq, psnr_db; } vnrAmdDecodeError;
+int    vnrAmdNeuralVolumeDecodeToDevice(vnrAmdVolume neural, void* d_out, int value_type, const int64_t strides[3],
+                                        const int box_lo[3], const int box_size[3], const int grid_dims[3],
+                                        float range_lo, float range_hi, void* stream);
+int    vnrAmdNeuralVolumeErrorAgainstDevice(vnrAmdVolume neural, const void* d_ref, int value_type, const int64_t strides[3],
+                                            const int box_lo[3], const int box_size[3], float range_lo, float range_hi,
+                                            void* stream, vnrAmdDecodeError* out, float* d_block_max);
 /* hash-grid encode only (tcnn_impl_decoder.cu:177-230, column = level*F + f): fp16 [n][padded_width] */
 int    vnrAmdNeuralVolumeEncode(vnrAmdVolume, size_t n, const float* d_coords, uint16_t* d_features, void* stream);
 /* AMD extension: state of the brick image, the de-hashed inference copy of the hashed levels (csrc/network.h).  It is built

@@ -51,6 +51,11 @@ class OutOfCoreInfo(C.Structure):
                 ("bytes_read", C.c_uint64)]
 
 
+class DecodeError(C.Structure):
+    _fields_ = [("n_voxels", C.c_uint64), ("max_abs", C.c_double), ("worst", C.c_int * 3), ("sum_abs", C.c_double), ("sum_sq", C.c_double),
+                ("psnr_db", C.c_double)]
+
+
 def declared_symbols():
     """every function name declared in include/vnr_amd.h"""
     text = open(HEADER).read()
@@ -231,6 +236,8 @@ def lib():
     sig("vnrAmdCreateSimpleVolumeFromDevice", P, P, IP, I, I64P, F, F, P, FP)
     sig("vnrAmdSimpleVolumeUpdateFromDevice", I, P, P, I, I64P, F, F, P, FP)
     sig("vnrAmdSimpleVolumeAppendTimeStepFromDevice", I, P, P, I, I64P, F, F, P, FP)
+    sig("vnrAmdNeuralVolumeDecodeToDevice", I, P, P, I, I64P, IP, IP, IP, F, F, P)
+    sig("vnrAmdNeuralVolumeErrorAgainstDevice", I, P, P, I, I64P, IP, IP, F, F, P, C.POINTER(DecodeError), P)
     _lib = L
     return L
 

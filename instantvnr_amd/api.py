@@ -433,6 +433,78 @@ def neural_decoded_volume(v, dims):
     return out
 
 
+def simple_volume_data_range(v):
+    """(lo, hi) in data units that the volume's normalised voxels stand for (vnrAmdSimpleVolumeGetDataRange)"""
+    r = np.zeros(2, np.float32)
+    check(lib().vnrAmdSimpleVolumeGetDataRange(v.h, _fp(r)))
+    return float(r[0]), float(r[1])
+
+
+def _box_args(box, grid_dims=None):
+    """checks and packs (lower, size) and the grid dims of the two round-trip calls; raises before the library is called"""
+    lo = size = g = None
+    if box is not None:
+        try:
+            lo_l, size_l = ([int(x) for x in np.atleast_1d(b)] for b in box)
+        except (TypeError, ValueError):
+            raise VnrAmdError(f"box must be (lower, size), three integers each, got {box!r}") from None
+        if len(lo_l) != 3 or len(size_l) != 3 or min(lo_l) < 0 or min(size_l) <= 0:
+            raise VnrAmdError(f"box must be (lower, size) with lower >= 0 and size > 0 on three axes, got {box!r}")
+        lo, size = (C.c_int * 3)(*lo_l), (C.c_int * 3)(*size_l)
+    if grid_dims is not None:
+        gl = [int(x) for x in np.atleast_1d(grid_dims)]
+        if len(gl) != 3 or min(gl) <= 0:
+            raise VnrAmdError(f"grid dims must be three positive sizes (x, y, z), got {grid_dims!r}")
+        g = (C.c_int * 3)(*gl)
+    return lo, size, g
+
+
+def _round_trip_range(dt, value_range):
+    if value_range is None:
+        if dt.kind != "f":
+            raise VnrAmdError(f"value range missing: the data type {dt} needs the (lo, hi) its integers stand for")
+        return 1.0, 0.0
+    lo, hi = (float(x) for x in value_range)
+    if not lo < hi:
+        raise VnrAmdError(f"value range must be (lo, hi) with lo < hi, got {value_range!r}")
+    return lo, hi
+
+
+def vnrNeuralVolumeDecodeToDevice(v, d_ptr, dtype, strides=None, box=None, grid_dims=None, value_range=None, stream=None):
+    """AMD extension (include/vnr_amd.h, "in-situ round trip"): the network at the voxel centres of `box` = (lower, size) of the grid
+    `grid_dims` (None: the whole grid / the volume's dims) -> typed voxels at `d_ptr`, the address of the box's first voxel in a
+    device array with element `strides` (None: dense over the box).  value_range (lo, hi) converts to data units (required for the
+    integer types; the ground truth's simple_volume_data_range inverts its ingest), None stores the normalised output.  stream =
+    the hipStream_t that may still be reading the array.  Returns after the decode has completed."""
+    p, _, t, s, _, _, st = _device_source_args(d_ptr, dtype, strides, None, stream)
+    lo, hi = _round_trip_range(np.dtype(dtype), value_range)
+    b_lo, b_size, g = _box_args(box, grid_dims)
+    check(lib().vnrAmdNeuralVolumeDecodeToDevice(v.h, p, t, s, b_lo, b_size, g, lo, hi, st))
+
+
+def vnrNeuralVolumeErrorAgainstDevice(v, d_ptr, dtype, strides=None, box=None, value_range=None, stream=None, block_map=False):
+    """the error of what vnrNeuralVolumeDecodeToDevice would store (same dtype and value_range) against the field at `d_ptr`, on the
+    volume's own grid -> dict(n_voxels, max_abs, worst (x, y, z), sum_abs, sum_sq, mean_abs, rmse, psnr_db); with block_map=True also
+    "block_max": max |error| per 16^3 macrocell as numpy [z, y, x]."""
+    p, _, t, s, _, _, st = _device_source_args(d_ptr, dtype, strides, None, stream)
+    lo, hi = _round_trip_range(np.dtype(dtype), value_range)
+    b_lo, b_size, _ = _box_args(box)
+    e = _lib.DecodeError()
+    cells = None
+    if block_map:
+        mc = (C.c_int * 3)()
+        check(lib().vnrAmdVolumeGetMacrocell(v.h, mc, None, None, None))
+        cells = DeviceArray((mc[2], mc[1], mc[0]), np.float32)
+    check(lib().vnrAmdNeuralVolumeErrorAgainstDevice(v.h, p, t, s, b_lo, b_size, lo, hi, st, C.byref(e), cells.ptr if cells else None))
+    n = int(e.n_voxels)
+    out = {"n_voxels": n, "max_abs": e.max_abs, "worst": tuple(e.worst), "sum_abs": e.sum_abs, "sum_sq": e.sum_sq,
+           "mean_abs": e.sum_abs / n, "rmse": float(np.sqrt(e.sum_sq / n)), "psnr_db": e.psnr_db}
+    if cells:
+        out["block_max"] = cells.numpy()
+        cells.free()
+    return out
+
+
 def vnrNeuralVolumeSerializeParams(v, filename=None):
     """with a filename: writes BSON params.json; without: returns the BSON bytes"""
     if filename is not None:

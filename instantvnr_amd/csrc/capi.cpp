@@ -571,6 +571,23 @@ const float* vnrAmdNeuralVolumeDecodedDeviceData(vnrAmdVolume v)
   guarded([&]() { r = as_neural(v)->decoded_data(); });
   return r;
 }
+int vnrAmdNeuralVolumeDecodeToDevice(vnrAmdVolume v, void* d_out, int value_type, const int64_t strides[3], const int box_lo[3],
+                                     const int box_size[3], const int grid_dims[3], float range_lo, float range_hi, void* stream)
+{
+  return guarded([&]() {
+    as_neural(v)->decode_to_device(DeviceTarget{d_out, value_type, strides, (hipStream_t)stream}, box_lo, box_size, grid_dims, range_lo, range_hi);
+  });
+}
+int vnrAmdNeuralVolumeErrorAgainstDevice(vnrAmdVolume v, const void* d_ref, int value_type, const int64_t strides[3], const int box_lo[3],
+                                         const int box_size[3], float range_lo, float range_hi, void* stream, vnrAmdDecodeError* out,
+                                         float* d_block_max)
+{
+  static_assert(sizeof(vnrAmdDecodeError) == sizeof(DecodeError), "vnrAmdDecodeError and vnr::DecodeError are one layout");
+  return guarded([&]() {
+    as_neural(v)->error_against_device(DeviceSource{d_ref, value_type, strides, (hipStream_t)stream}, box_lo, box_size, range_lo, range_hi,
+                                       reinterpret_cast<DecodeError*>(out), d_block_max);
+  });
+}
 int vnrAmdNeuralVolumeSerializeParamsToFile(vnrAmdVolume v, const char* filename)
 {
   return guarded([&]() {

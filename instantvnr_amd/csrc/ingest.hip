@@ -237,6 +237,8 @@ struct EventGuard {
 
 }  // namespace
 
+size_t device_value_type_size(int type) { return ingest_type_size(type); }
+
 void SimpleVolume::validate_device_source(const DeviceSource& src, vec3i dims) const
 {
   if (!src.data) throw std::runtime_error("null device data");

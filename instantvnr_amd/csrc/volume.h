@@ -89,6 +89,26 @@ struct DeviceSource {
   hipStream_t producer = nullptr;
 };
 
+// bytes of a value type device data may have (ingest.hip); throws, by name, for the 64-bit integer, the vector and unknown types
+size_t device_value_type_size(int type);
+
+// Typed voxels in device memory to be written (decode.hip): as DeviceSource; `consumer` is the stream that may still be reading what
+// the array holds (null: nobody is).
+struct DeviceTarget {
+  void* data = nullptr;
+  int type = 8;
+  const int64_t* strides = nullptr;
+  hipStream_t consumer = nullptr;
+};
+
+// vnrAmdDecodeError (include/vnr_amd.h), field for field
+struct DecodeError {
+  uint64_t n_voxels;
+  double max_abs;
+  int worst[3];
+  double sum_abs, sum_sq, psnr_db;
+};
+
 struct VolumeDesc {  // MultiVolume, instantvnr_types.h:40-56 (single timestep)
   vec3i dims{0, 0, 0};
   int type = 8;  // VALUE_TYPE_FLOAT
@@ -204,6 +224,15 @@ public:
   // full pass; the blob cursor is per volume here, a function-local static in the reference).
   void decode_progressive();
   const float* decoded_data() const { return decoded_.count ? decoded_.ptr : nullptr; }
+  // In-situ round trip (decode.hip; no reference counterpart).  decode_to_device: the network at the voxel centres of a box of a
+  // grid (null grid_dims: the volume's; null box: the whole grid) -> the caller's typed array, in data units when range_lo <
+  // range_hi.  error_against_device: the error of exactly those typed voxels against a field on the volume's own grid, reduced
+  // chunk by chunk (the decoded box is never stored); d_block_max (may be null): max |error| per macrocell.  Both validate first
+  // (a refused call has touched nothing), run in chunks of VNR_AMD_DECODE_CHUNK samples through scratch kept here, and return
+  // after the work has completed.
+  void decode_to_device(const DeviceTarget& out, const int box_lo[3], const int box_size[3], const int grid_dims[3], float range_lo, float range_hi);
+  void error_against_device(const DeviceSource& ref, const int box_lo[3], const int box_size[3], float range_lo, float range_hi, DecodeError* result,
+                            float* d_block_max);
   // network.cu:328-365 / :367-405: raw fp32, z-slice by z-slice, every slice padded to a multiple of 256 values
   void save_inference_volume(const std::string& filename);
   void save_reference_volume(const std::string& filename);
@@ -223,6 +252,10 @@ private:
   DeviceBuffer<float> train_x_{MemTag::Network}, train_y_{MemTag::Network}, test_y1_{MemTag::Network};
   DeviceBuffer<float> decoded_{MemTag::Network}, decode_coords_{MemTag::Network};  // dense decoded volume, coordinates of one blob
   int decode_blob_ = 0;
+  // decode.hip: coordinates and values of one chunk, block partials of the error report + its result; grown on demand, then kept
+  DeviceBuffer<float> dd_coords_{MemTag::Network}, dd_values_{MemTag::Network};
+  DeviceBuffer<double> dd_partials_{MemTag::Network};
+  void decode_chunk(uint64_t b, uint32_t n, uint64_t bx, uint64_t by, vec3i lower, vec3f rdims, float* d_values);
   bool pending_step_ = false, pending_internal_ = false;
   bool replicas_synced_ = false;
   uint64_t synced_generation_ = 0;   // Network::params_generation() at the last sync_replicas

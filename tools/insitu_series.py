@@ -15,13 +15,23 @@ ingest time are printed.
   --range-from-data      min / max of every step instead of the type's range (reads the source twice)
   --repeat R             time every ingest R times, report the fastest and the median          [5]
   --compare-host         also time vnrAmdCreateSimpleVolumeFromMemory on the same array (the path a host-resident field takes)
+  --round-trip           after each step's training: the error of the decoded voxels against the step's own device array, in data units
+                         (vnrAmdNeuralVolumeErrorAgainstDevice), and a decode into a device array of the source's type and ghost
+                         layers (vnrAmdNeuralVolumeDecodeToDevice); both timed, beside vnrAmdNeuralVolumeInference on the same
+                         number of ready-made coordinates
   --seed N                                                                                     [1]
 
 Times are host clocks around calls that end in a device synchronise.  "update" is the whole vnrAmdSimpleVolumeUpdateFromDevice call
 (ingest kernels + macrocell pass); "macrocell" is the macrocell pass alone (vnrAmdSimpleVolumeSetCurrentTimeStep on the current step);
 "ingest" is their difference, and the GB/s are the bytes the ingest must move (source bytes once or twice + 4 bytes written per voxel)
 over it.  Kernel times proper: run this under rocprofv3 --kernel-trace --stats (the kernels are ingest_minmax_kernel,
-ingest_minmax_final_kernel, ingest_convert_kernel)."""
+ingest_minmax_final_kernel, ingest_convert_kernel).
+
+The --round-trip times are host clocks as well, each around one call that returns after its work has completed: "decode" and
+"error" are the whole calls (coordinate kernel + evaluation + store or reduce kernel per chunk of VNR_AMD_DECODE_CHUNK samples),
+"inference" is one vnrAmdNeuralVolumeInference call + synchronise over the same voxel centres as ready-made coordinates, so
+"decode - inference" is a difference of wall times.  Each is run once to warm up, then --repeat times.  The kernels are decode_coords_kernel, decode_store_kernel,
+decode_error_kernel and decode_error_final_kernel."""
 import argparse
 import json
 import os
@@ -61,13 +71,39 @@ def with_ghost_layers(a, g):
     return p, g + g * sy + g * sz, (1, sy, sz)
 
 
-def timed(fn, repeat):
+def timed(fn, repeat, warmup=0):
     out, times = None, []
+    for _ in range(warmup):
+        fn()
     for _ in range(repeat):
         t0 = time.perf_counter()
         out = fn()
         times.append((time.perf_counter() - t0) * 1e3)
     return out, min(times), statistics.median(times)
+
+
+def round_trip(neural, ptr, dtype, strides, dims, ghost, value_range, repeat, coords):
+    """-> the --round-trip columns of one step.  `ptr` is the step's own device array (the reference of the error report)."""
+    n = dims[0] * dims[1] * dims[2]
+    rep, best, median = timed(lambda: api.vnrNeuralVolumeErrorAgainstDevice(neural, ptr, dtype, strides, None, value_range), repeat, 1)
+    row = {"max_abs_error": rep["max_abs"], "worst_voxel": list(rep["worst"]), "mean_abs_error": rep["mean_abs"],
+           "psnr_data_units_db": round(rep["psnr_db"], 3), "error_ms": round(best, 4), "error_median_ms": round(median, 4)}
+    padded = tuple(d + 2 * ghost for d in dims)
+    out = api.DeviceArray((padded[2], padded[1], padded[0]), dtype)     # the array a consumer would hand over, ghost layers included
+    first = (ghost + ghost * padded[0] + ghost * padded[0] * padded[1]) * dtype.itemsize
+    _, best, median = timed(lambda: api.vnrNeuralVolumeDecodeToDevice(neural, out.ptr + first, dtype, strides, None, None, value_range), repeat, 1)
+    out.free()
+    row.update(decode_ms=round(best, 4), decode_median_ms=round(median, 4))
+    values = api.DeviceArray((n,), np.float32)
+
+    def inference():
+        api.check(api.lib().vnrAmdNeuralVolumeInference(neural.h, n, coords.ptr, values.ptr, None))
+        api.check(api.lib().vnrAmdSynchronize())
+    _, best, median = timed(inference, repeat, 1)
+    values.free()
+    row.update(inference_ms=round(best, 4), inference_median_ms=round(median, 4), samples=n,
+               decode_chunk=int(os.environ.get("VNR_AMD_DECODE_CHUNK", 1 << 22)))
+    return row
 
 
 def main(argv=None):
@@ -80,8 +116,11 @@ def main(argv=None):
     p.add_argument("--range-from-data", action="store_true")
     p.add_argument("--repeat", type=int, default=5)
     p.add_argument("--compare-host", action="store_true")
+    p.add_argument("--round-trip", action="store_true")
     p.add_argument("--seed", type=int, default=1)
     a = p.parse_args(argv)
+    if a.round_trip and not a.steps_per_frame:
+        p.error("--round-trip needs a trained network: --steps-per-frame > 0")
 
     api._lib.require_device()
     api.check(api.lib().vnrAmdInit(-1))
@@ -94,7 +133,13 @@ def main(argv=None):
     print(f"library build {api.lib().vnrAmdBuildId().decode()}; {a.size}^3 {a.dtype}, ghost {a.ghost}, range "
           f"{'from the data' if a.range_from_data else value_range}, ingest reads {bytes_read} B and writes {bytes_written} B")
 
-    volume = neural = None
+    volume = neural = coords = None
+    if a.round_trip:     # ready-made coordinates for the plain inference: the voxel centres, x fastest (12 bytes per voxel)
+        c = (np.arange(a.size, dtype=np.float32) + np.float32(0.5)) * (np.float32(1.0) / np.float32(a.size))
+        host = np.empty((a.size, a.size, a.size, 3), np.float32)
+        host[..., 0], host[..., 1], host[..., 2] = c[None, None, :], c[None, :, None], c[:, None, None]
+        coords = api.DeviceArray.from_numpy(host.reshape(-1, 3))
+        del host
     for t, step in enumerate(series(a.size, a.frames, dtype, a.seed)):
         source, offset, strides = with_ghost_layers(step, a.ghost)
         d = api.DeviceArray.from_numpy(source)              # the "simulation output": typed voxels in device memory
@@ -116,12 +161,14 @@ def main(argv=None):
             host, row["host_create_ms"], row["host_create_median_ms"] = timed(lambda: api.vnrCreateSimpleVolume(step, value_range=value_range),
                                                                                1 if t == 0 else min(a.repeat, 3))
             host.release()
-        d.free()
         if neural is not None:
             t0 = time.perf_counter()
             api.vnrNeuralVolumeTrain(neural, a.steps_per_frame, True)
             row["train_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
             row["psnr"] = round(api.vnrNeuralVolumeGetPSNR(neural), 3)
+            if a.round_trip:     # in data units: the range that was applied inverts the ingest
+                row.update(round_trip(neural, ptr, dtype, strides, dims, a.ghost, used, a.repeat, coords))
+        d.free()
         for k in ("create_ms", "host_create_ms", "host_create_median_ms"):
             if k in row:
                 row[k] = round(row[k], 4)

@@ -530,6 +530,70 @@ void vnrAmdFreeTemporaryGPUMemory(void);                                   /* vn
 /* StaticSampler::sample (neural_sampler.cu:130-164): n uniform coords in [lower,upper] + cell-centred trilinear values */
 int  vnrAmdSimpleVolumeTakeSamples(vnrAmdVolume, size_t n, const float lower[3], const float upper[3],
                                    float* d_coords, float* d_values, void* stream);
+/* AMD extension: error-guided training batches.  A simple volume with resident voxels may carry a SAMPLING TABLE: one weight per
+ * 16^3 macrocell, from which training batches are drawn instead of uniformly over the volume.  The layout of d_weights is the
+ * one of d_block_max of vnrAmdNeuralVolumeErrorAgainstDevice (dims and order of vnrAmdVolumeGetMacrocell: x fastest, ragged last
+ * cells), so an error map goes in unchanged: "where the error is" becomes "where to train more".
+ *   d_weights         one float per macrocell, a pointer of the library's HIP runtime (as d_data of the ingest); NULL removes the table.
+ *   uniform_fraction  in [0, 1]: the share of every batch that is still drawn uniformly over the whole volume.
+ *   stream            as for the ingest: the hipStream_t d_weights was produced on (NULL = complete); the library records an event
+ *                     on it and makes its own stream wait; the caller's stream is never blocked.
+ * The call returns after the table is complete (the caller may overwrite or free d_weights).  The table is built into new memory,
+ * the call waits for the draws in flight that may still read the old one, and swaps only on success: a refused call leaves the
+ * old table in force.  The table belongs to the volume: it survives vnrAmdSimpleVolumeSetCurrentTimeStep and
+ * vnrAmdSimpleVolumeUpdateFromDevice (same dims; a stale map is still a valid weighting) and is released with the volume.
+ *
+ * The table, all of it exact (integers, or one rounding each in double):
+ *   validation   wmax = the unsigned maximum over the float BITS of the entries without a sign bit (for non-negative floats that
+ *                is their maximum); an entry that is a NaN, an infinity or negative refuses the call, and so does wmax == 0
+ *                (-0.0f counts as 0).
+ *   quantisation q[c] = (uint64) rint(((double)w[c] / (double)wmax) * 16777216.0), ties to even; w[c] > 0 with q[c] == 0 gets
+ *                q[c] = 1: a cell with any error is never starved, a cell with weight 0 is reached through the uniform share only.
+ *   CDF          cdf[c] = q[0] + ... + q[c], uint64, in cell order (a device scan; integer sums do not depend on how they are
+ *                parallelised); total = cdf[n_cells - 1] <= n_cells * 2^24.
+ *   threshold    T = (uint64) rint((double)uniform_fraction * 4294967296.0).
+ * The draw.  TakeSamplesWeighted continues the volume's pcg32 stream, the seed / sequence / offset vnrAmdSimpleVolumeTakeSamples
+ * uses (vnrAmdNeuralVolumeSetSamplerSeed).  Sample e of a call consumes exactly six draws, stream positions offset + 6e .. 6e + 5,
+ * and the call advances the offset by 6n whichever branch a sample takes:
+ *   draw 0       s = next_uint; the sample is uniform iff (uint64)s < T.
+ *   draws 1, 2   r = ((uint64)next_uint << 32) | next_uint, k = the high 64 bits of r * total (__umul64hi); the cell is the first c
+ *                with cdf[c] > k (an upper bound; cells with q = 0 are never chosen).  Always made, ignored in the uniform branch.
+ *   draws 3 - 5  ux, uy, uz = next_float = uint_as_float((next_uint >> 9) | 0x3f800000) - 1.0f.
+ *   uniform      p = (ux, uy, uz): what TakeSamples computes for the unit box.
+ *   weighted     per axis, with lo = 16 * c_axis and size = min(16, dims - lo):
+ *                  p = fminf(__fmul_rn(__fadd_rn((float)lo, __fmul_rn(u, (float)size)), 1.0f / (float)dims), 0x1.fffffep-1f)
+ *                three fp32 roundings, never an fma; the reciprocal in fp32, as the decode's coordinates; the clamp keeps p < 1 like
+ *                the uniform stream.  A sample may land on its cell's upper face by rounding; that is harmless.
+ *   value        the cell-centred trilinear lookup of TakeSamples at p.
+ * d_coords [n][3] and d_values [n] are device arrays; `stream` of TakeSamplesWeighted is the stream the kernel runs on (NULL = the
+ * library's), as for TakeSamples.  The search of the CDF first looks through a strided top of it staged in LDS; VNR_AMD_GUIDED_LDS=0
+ * (read when weights are set) searches global memory alone.  Same bits either way.
+ *
+ * Training: while the ground truth of a neural volume has a table, vnrAmdNeuralVolumeTrain, ...TrainBegin and
+ * ...TrainDataParallel draw their batches from it (6 draws per sample); vnrAmdNeuralVolumeGetTrainingLoss then reports the loss
+ * of guided batches.  GetTestingLoss, GetPSNR, GetSSIM, the decode paths and TakeSamples stay uniform and consume the stream as
+ * before (3 draws per sample).  Setting weights is the opt-in: without a table every path runs the code it ran before.  The online
+ * macrocell update takes a guided batch as it takes any batch, and deterministic training composes: a batch is a pure function of
+ * seed, offset and table.  Data-parallel: every rank draws from its own volume's table with its own sequence; the ranks must
+ * install the same weights (not checked).
+ *
+ * SamplingInfo (any output may be NULL): active = 1 with a table; n_cells, total, uniform_fraction of the table (0 without).
+ * SamplingCdf: the device pointer of the CDF (n_cells uint64), NULL when there is no table or on error.
+ *
+ * GuideSamplingByError closes the loop in one call, for a neural volume whose ground truth is resident in the library: the error
+ * pass of ErrorAgainstDevice against the ground truth's current float voxels (vnrAmdSimpleVolumeDeviceData, VNR_AMD_TYPE_FLOAT,
+ * the whole volume, no range), then its per-macrocell maxima as the ground truth's weights.  It equals the two public calls made
+ * by hand, bit for bit: same report (may be NULL), same CDF.
+ *
+ * Errors (VNR_AMD_ERROR and a message; the previous table stays in force): uniform_fraction a NaN or outside [0, 1], a null
+ * volume, a neural volume (Set / Info / Cdf / TakeSamplesWeighted) or a simple one (GuideSamplingByError), an out-of-core or
+ * "NOTHING" volume (no resident voxels), weights with a NaN, an infinity or a negative value, all-zero weights (for
+ * GuideSamplingByError: a perfect fit), TakeSamplesWeighted without a table, no resident ground truth, no usable device. */
+int  vnrAmdSimpleVolumeSetSamplingWeights(vnrAmdVolume simple, const float* d_weights, float uniform_fraction, void* stream);
+int  vnrAmdSimpleVolumeSamplingInfo(vnrAmdVolume simple, int* active, uint64_t* n_cells, uint64_t* total, float* uniform_fraction);
+const uint64_t* vnrAmdSimpleVolumeSamplingCdf(vnrAmdVolume simple);
+int  vnrAmdSimpleVolumeTakeSamplesWeighted(vnrAmdVolume simple, size_t n, float* d_coords, float* d_values, void* stream);
+int  vnrAmdNeuralVolumeGuideSamplingByError(vnrAmdVolume neural, float uniform_fraction, vnrAmdDecodeError* report);
 /* SamplerAPI::sample_grid (neural_sampler.cu:166-198; out-of-core: sample_streaming_grid, neural_sampler.cpp:967-1035):
  * voxel-centre coordinates of the block [origin, origin + size) of the volume's grid and the ground truth there */
 int  vnrAmdSimpleVolumeTakeSamplesGrid(vnrAmdVolume, const int origin[3], const int size[3], float* d_coords, float* d_values,

@@ -238,6 +238,12 @@ def lib():
     sig("vnrAmdSimpleVolumeAppendTimeStepFromDevice", I, P, P, I, I64P, F, F, P, FP)
     sig("vnrAmdNeuralVolumeDecodeToDevice", I, P, P, I, I64P, IP, IP, IP, F, F, P)
     sig("vnrAmdNeuralVolumeErrorAgainstDevice", I, P, P, I, I64P, IP, IP, F, F, P, C.POINTER(DecodeError), P)
+    U64P = C.POINTER(U64)
+    sig("vnrAmdSimpleVolumeSetSamplingWeights", I, P, P, F, P)
+    sig("vnrAmdSimpleVolumeSamplingInfo", I, P, IP, U64P, U64P, FP)
+    sig("vnrAmdSimpleVolumeSamplingCdf", P, P)
+    sig("vnrAmdSimpleVolumeTakeSamplesWeighted", I, P, SZ, P, P, P)
+    sig("vnrAmdNeuralVolumeGuideSamplingByError", I, P, F, C.POINTER(DecodeError))
     _lib = L
     return L
 

@@ -470,6 +470,12 @@ def _round_trip_range(dt, value_range):
     return lo, hi
 
 
+def _decode_error_dict(e):
+    n = int(e.n_voxels)
+    return {"n_voxels": n, "max_abs": e.max_abs, "worst": tuple(e.worst), "sum_abs": e.sum_abs, "sum_sq": e.sum_sq,
+            "mean_abs": e.sum_abs / n, "rmse": float(np.sqrt(e.sum_sq / n)), "psnr_db": e.psnr_db}
+
+
 def vnrNeuralVolumeDecodeToDevice(v, d_ptr, dtype, strides=None, box=None, grid_dims=None, value_range=None, stream=None):
     """AMD extension (include/vnr_amd.h, "in-situ round trip"): the network at the voxel centres of `box` = (lower, size) of the grid
     `grid_dims` (None: the whole grid / the volume's dims) -> typed voxels at `d_ptr`, the address of the box's first voxel in a
@@ -496,9 +502,7 @@ def vnrNeuralVolumeErrorAgainstDevice(v, d_ptr, dtype, strides=None, box=None, v
         check(lib().vnrAmdVolumeGetMacrocell(v.h, mc, None, None, None))
         cells = DeviceArray((mc[2], mc[1], mc[0]), np.float32)
     check(lib().vnrAmdNeuralVolumeErrorAgainstDevice(v.h, p, t, s, b_lo, b_size, lo, hi, st, C.byref(e), cells.ptr if cells else None))
-    n = int(e.n_voxels)
-    out = {"n_voxels": n, "max_abs": e.max_abs, "worst": tuple(e.worst), "sum_abs": e.sum_abs, "sum_sq": e.sum_sq,
-           "mean_abs": e.sum_abs / n, "rmse": float(np.sqrt(e.sum_sq / n)), "psnr_db": e.psnr_db}
+    out = _decode_error_dict(e)
     if cells:
         out["block_max"] = cells.numpy()
         cells.free()
@@ -827,6 +831,80 @@ def simple_volume_take_samples(v, n, lower=(0, 0, 0), upper=(1, 1, 1)):
     check(lib().vnrAmdSimpleVolumeTakeSamples(v.h, n, _fp(_vec(lower)), _fp(_vec(upper)), c.ptr, o.ptr, None))
     check(lib().vnrAmdSynchronize())
     return c.numpy(), o.numpy()
+
+
+def _uniform_fraction(uniform_fraction):
+    """checks the share of a guided batch that stays uniform; raises before the library is called"""
+    try:
+        f = float(uniform_fraction)
+    except (TypeError, ValueError):
+        raise VnrAmdError(f"uniform_fraction must be a number in [0, 1], got {uniform_fraction!r}") from None
+    if not 0.0 <= f <= 1.0:
+        raise VnrAmdError(f"uniform_fraction must lie in [0, 1], got {uniform_fraction!r}")
+    return f
+
+
+def simple_volume_set_sampling_weights(v, weights, uniform_fraction=0.0, stream=None):
+    """AMD extension (include/vnr_amd.h, "error-guided training batches"): one weight per 16^3 macrocell, from which training batches
+    are then drawn.  `weights` is a numpy array with one float per cell ([z, y, x] or flat, x fastest; the "block_max" of
+    vnrNeuralVolumeErrorAgainstDevice as it is), a DeviceArray or a raw device address, or None to remove the table;
+    uniform_fraction in [0, 1] is the share of every batch that stays uniform."""
+    f = _uniform_fraction(uniform_fraction)
+    st = C.c_void_p(stream) if stream else None
+    if weights is None:
+        check(lib().vnrAmdSimpleVolumeSetSamplingWeights(v.h, None, f, st))
+        return
+    if isinstance(weights, DeviceArray) or isinstance(weights, int):
+        ptr = weights.ptr if isinstance(weights, DeviceArray) else weights
+        if not ptr:
+            raise VnrAmdError("null device weights")
+        check(lib().vnrAmdSimpleVolumeSetSamplingWeights(v.h, C.c_void_p(ptr), f, st))
+        return
+    w = np.ascontiguousarray(weights, dtype=np.float32).ravel()
+    n_cells = int(np.prod([(d + 15) // 16 for d in vnrVolumeGetDims(v)]))
+    if w.size != n_cells:
+        raise VnrAmdError(f"the weights hold {w.size} values, the volume has {n_cells} macrocells")
+    d = DeviceArray.from_numpy(w)
+    try:
+        check(lib().vnrAmdSimpleVolumeSetSamplingWeights(v.h, C.c_void_p(d.ptr), f, st))
+    finally:
+        d.free()
+
+
+def simple_volume_sampling_info(v):
+    """-> dict(active, n_cells, total, uniform_fraction) of the volume's sampling table (zeros without one)"""
+    active, n_cells, total, f = C.c_int(), C.c_uint64(), C.c_uint64(), C.c_float()
+    check(lib().vnrAmdSimpleVolumeSamplingInfo(v.h, C.byref(active), C.byref(n_cells), C.byref(total), C.byref(f)))
+    return {"active": bool(active.value), "n_cells": int(n_cells.value), "total": int(total.value), "uniform_fraction": float(f.value)}
+
+
+def simple_volume_sampling_cdf(v):
+    """the table's CDF as numpy uint64 [n_cells], or None without a table"""
+    info = simple_volume_sampling_info(v)
+    p = lib().vnrAmdSimpleVolumeSamplingCdf(v.h)
+    if not info["active"] or not p:
+        return None
+    out = np.empty(info["n_cells"], np.uint64)
+    check(lib().vnrAmdMemcpyD2H(out.ctypes.data_as(C.c_void_p), p, out.nbytes))
+    return out
+
+
+def simple_volume_take_samples_weighted(v, n):
+    """n samples drawn from the volume's sampling table -> (coords [n, 3], values [n]); continues the volume's pcg32 stream"""
+    c = DeviceArray((n, 3), np.float32)
+    o = DeviceArray((n,), np.float32)
+    check(lib().vnrAmdSimpleVolumeTakeSamplesWeighted(v.h, n, c.ptr, o.ptr, None))
+    check(lib().vnrAmdSynchronize())
+    return c.numpy(), o.numpy()
+
+
+def neural_volume_guide_sampling_by_error(v, uniform_fraction=0.0):
+    """the error report of the neural volume against its resident ground truth, whose per-macrocell maxima become the ground truth's
+    sampling weights -> the report (the dict of vnrNeuralVolumeErrorAgainstDevice without "block_max")"""
+    f = _uniform_fraction(uniform_fraction)
+    e = _lib.DecodeError()
+    check(lib().vnrAmdNeuralVolumeGuideSamplingByError(v.h, f, C.byref(e)))
+    return _decode_error_dict(e)
 
 
 def neural_forward_backward(v, coords, targets):

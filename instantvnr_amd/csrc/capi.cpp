@@ -1094,6 +1094,41 @@ int vnrAmdSimpleVolumeTakeSamples(vnrAmdVolume v, size_t n, const float lower[3]
     as_simple(v)->take_samples(d_coords, d_values, n, {lower[0], lower[1], lower[2]}, {upper[0], upper[1], upper[2]}, resolve_stream(stream));
   });
 }
+int vnrAmdSimpleVolumeSetSamplingWeights(vnrAmdVolume v, const float* d_weights, float uniform_fraction, void* stream)
+{
+  return guarded([&]() {
+    SimpleVolume::check_uniform_fraction(uniform_fraction);   // an argument check: before the handle, so that it needs no volume
+    as_simple(v)->set_sampling_weights(d_weights, uniform_fraction, (hipStream_t)stream);
+  });
+}
+int vnrAmdSimpleVolumeSamplingInfo(vnrAmdVolume v, int* active, uint64_t* n_cells, uint64_t* total, float* uniform_fraction)
+{
+  return guarded([&]() {
+    const SimpleVolume* sv = as_simple(v);
+    if (active) *active = sv->has_sampling_table() ? 1 : 0;
+    if (n_cells) *n_cells = sv->sampling_cells();
+    if (total) *total = sv->sampling_total();
+    if (uniform_fraction) *uniform_fraction = sv->sampling_uniform_fraction();
+  });
+}
+const uint64_t* vnrAmdSimpleVolumeSamplingCdf(vnrAmdVolume v)
+{
+  const uint64_t* p = nullptr;
+  guarded([&]() { p = as_simple(v)->sampling_cdf(); });
+  return p;
+}
+int vnrAmdSimpleVolumeTakeSamplesWeighted(vnrAmdVolume v, size_t n, float* d_coords, float* d_values, void* stream)
+{
+  return guarded([&]() { as_simple(v)->take_samples_weighted(d_coords, d_values, n, resolve_stream(stream)); });
+}
+int vnrAmdNeuralVolumeGuideSamplingByError(vnrAmdVolume v, float uniform_fraction, vnrAmdDecodeError* report)
+{
+  static_assert(sizeof(vnrAmdDecodeError) == sizeof(DecodeError), "vnrAmdDecodeError and DecodeError must agree");
+  return guarded([&]() {
+    SimpleVolume::check_uniform_fraction(uniform_fraction);
+    as_neural(v)->guide_sampling_by_error(uniform_fraction, (DecodeError*)report);
+  });
+}
 int vnrAmdSimpleVolumeTakeSamplesGrid(vnrAmdVolume v, const int origin[3], const int size[3], float* d_coords, float* d_values, void* stream)
 {
   return guarded([&]() {

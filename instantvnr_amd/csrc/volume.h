@@ -169,6 +169,20 @@ public:
   // data-parallel training: rank r draws pcg32 stream (default stream + r) unless the application chose a stream itself
   void set_sampler_rank(int rank) { if (!rng_user_set_) { rng_stream_ = 0xda3e39cb94b95bdbULL + (uint64_t)rank; rng_offset_ = 0; } }
 
+  // Error-guided sampling (guided_sampler.hip; no reference counterpart; the arithmetic is spelled out in include/vnr_amd.h).
+  // set_sampling_weights: one float per macrocell (x fastest) -> a uint64 CDF of 24-bit quantised weights, built into new memory and
+  // swapped in on success only, after the draws that may still read the old table have finished (the library's stream and every
+  // other stream a draw was launched on are synchronised; nothing is recorded per draw); null weights remove the table.
+  // take_samples_weighted: n samples from the table, six draws of the sampler's pcg32 stream each; throws without a table.
+  static void check_uniform_fraction(float uniform_fraction);   // throws, by name, unless it lies in [0, 1]
+  void set_sampling_weights(const float* d_weights, float uniform_fraction, hipStream_t producer);
+  void take_samples_weighted(float* d_coords, float* d_values, size_t n, hipStream_t s);
+  bool has_sampling_table() const { return table_.cdf.ptr != nullptr; }
+  const uint64_t* sampling_cdf() const { return table_.cdf.ptr; }
+  uint64_t sampling_cells() const { return table_.n_cells; }
+  uint64_t sampling_total() const { return table_.total; }
+  float sampling_uniform_fraction() const { return table_.uniform_fraction; }
+
 private:
   void finish_load(hipStream_t s);
   void validate_device_source(const DeviceSource& src, vec3i dims) const;
@@ -183,6 +197,15 @@ private:
   TfnObject tfn_;
   uint64_t rng_seed_ = 1337, rng_stream_ = 0xda3e39cb94b95bdbULL, rng_offset_ = 0;  // neural_sampler.cu:36
   bool rng_user_set_ = false;
+  struct SamplingTable {
+    DeviceBuffer<uint64_t> cdf;   // inclusive prefix sums of the quantised weights, one per macrocell
+    uint64_t n_cells = 0, total = 0, threshold = 0;   // threshold: draw 0 below it takes the uniform branch
+    float uniform_fraction = 0.0f;
+    vec3i cells{0, 0, 0};
+    bool staged = false;          // the draw searches a strided top of the CDF in LDS first
+  } table_;
+  DeviceBuffer<uint64_t> table_scratch_;   // block sums of the scan's upper levels + the validation pass's result
+  std::vector<hipStream_t> table_streams_;  // the callers' streams that drew from the table since it was installed: what a table swap waits for
 };
 
 class NeuralVolume : public VolumeBase {  // core/network.h:29-107, core/network.cu:143-699
@@ -236,6 +259,9 @@ public:
   // network.cu:328-365 / :367-405: raw fp32, z-slice by z-slice, every slice padded to a multiple of 256 values
   void save_inference_volume(const std::string& filename);
   void save_reference_volume(const std::string& filename);
+  // Error-guided sampling in one call (guided_sampler.hip): error_against_device over the whole volume against the resident ground
+  // truth's float voxels, then its per-macrocell maxima as the ground truth's sampling weights.  report may be null.
+  void guide_sampling_by_error(float uniform_fraction, DecodeError* report);
 
   Network& network() { return net_; }
   SimpleVolume* source() { return source_; }

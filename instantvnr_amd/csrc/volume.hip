@@ -10,6 +10,7 @@
 #include <thread>
 
 #include "dist.h"
+#include "pcg32_device.h"
 #include "sampling_device.h"
 #include "scene.h"
 
@@ -234,31 +235,7 @@ void MacroCell::upload_value_range(const void* host, size_t bytes, hipStream_t s
 }
 
 // ================================================================================================ sampler kernels
-struct Pcg32Dev {
-  uint64_t state, inc;
-  __device__ Pcg32Dev(uint64_t initstate, uint64_t initseq)
-  {
-    state = 0u; inc = (initseq << 1u) | 1u; next_uint(); state += initstate; next_uint();
-  }
-  __device__ uint32_t next_uint()
-  {
-    const uint64_t old = state;
-    state = old * 0x5851f42d4c957f2dULL + inc;
-    const uint32_t xs = (uint32_t)(((old >> 18u) ^ old) >> 27u), rot = (uint32_t)(old >> 59u);
-    return (xs >> rot) | (xs << ((~rot + 1u) & 31));
-  }
-  __device__ float next_float() { const uint32_t u = (next_uint() >> 9) | 0x3f800000u; return __uint_as_float(u) - 1.0f; }
-  __device__ void advance(uint64_t delta)
-  {
-    uint64_t cm = 0x5851f42d4c957f2dULL, cp = inc, am = 1u, ap = 0u;
-    while (delta > 0) {
-      if (delta & 1) { am *= cm; ap = ap * cm + cp; }
-      cp = (cm + 1) * cp; cm *= cm; delta >>= 1;
-    }
-    state = am * state + ap;
-  }
-};
-
+// (Pcg32Dev: pcg32_device.h, shared with guided_sampler.hip)
 // neural_sampler.cu:130-164: p = lower + u * (upper - lower), value = tex3D(p) (cell-centred, clamp).
 // The random stream is pcg32(seed 1337) like tcnn's generate_random_uniform; element e of the call draws the
 // (offset + e)-th float of the stream (tcnn's thread-to-element mapping is EXTERNAL and not reproduced).
@@ -814,7 +791,9 @@ void NeuralVolume::train_begin()
   if (!net_.valid()) return;
   if (!source_) throw std::runtime_error("missing a reference volume");  // network.cu:233-235 prints and returns
   const vec3f lower = {0, 0, 0}, upper = {1, 1, 1};  // m_lower/m_upper = full volume (network.cu:605)
-  source_->take_samples(train_x_.ptr, train_y_.ptr, batch_size_, lower, upper, stream);
+  // a ground truth with sampling weights hands out error-guided batches (guided_sampler.hip); without them this is the code it always was
+  if (source_->has_sampling_table()) source_->take_samples_weighted(train_x_.ptr, train_y_.ptr, batch_size_, stream);
+  else source_->take_samples(train_x_.ptr, train_y_.ptr, batch_size_, lower, upper, stream);
   net_.forward_backward(train_x_.ptr, train_y_.ptr, batch_size_, stream);
   pending_step_ = true;
   pending_internal_ = true;
@@ -955,7 +934,9 @@ void NeuralVolume::train_data_parallel(size_t steps, bool fast_mode)
   if (!dp.sharded && net_.opt_sharded()) sync_replicas();   // the shape was switched between calls
   const vec3f lower = {0, 0, 0}, upper = {1, 1, 1};
   for (size_t i = 0; i < steps; ++i) {
-    source_->take_samples(train_x_.ptr, train_y_.ptr, batch_size_, lower, upper, stream);
+    // (every rank draws from ITS ground truth's table with its own sequence: the ranks must have installed the same weights)
+    if (source_->has_sampling_table()) source_->take_samples_weighted(train_x_.ptr, train_y_.ptr, batch_size_, stream);
+    else source_->take_samples(train_x_.ptr, train_y_.ptr, batch_size_, lower, upper, stream);
     dp.ranges.clear();
     dp.used = 0;
     net_.forward_backward(train_x_.ptr, train_y_.ptr, batch_size_, stream, &dp);

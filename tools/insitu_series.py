@@ -19,6 +19,12 @@ ingest time are printed.
                          (vnrAmdNeuralVolumeErrorAgainstDevice), and a decode into a device array of the source's type and ghost
                          layers (vnrAmdNeuralVolumeDecodeToDevice); both timed, beside vnrAmdNeuralVolumeInference on the same
                          number of ready-made coordinates
+  --guided               error-guided batches instead of the series (vnrAmdNeuralVolumeGuideSamplingByError): ONE static field, the
+                         synthetic blob field with plateaus at both ends, trained --steps-per-frame steps in all, twice with the same
+                         seeds: once with the error map re-installed as sampling weights every --refresh-every steps, once with
+                         uniform batches.  After each refresh: the maximum error and the PSNR of both
+  --uniform-fraction F   the share of a guided batch that stays uniform                         [0.25]
+  --refresh-every N      steps between two error reports / weight maps                          [100]
   --seed N                                                                                     [1]
 
 Times are host clocks around calls that end in a device synchronise.  "update" is the whole vnrAmdSimpleVolumeUpdateFromDevice call
@@ -106,6 +112,49 @@ def round_trip(neural, ptr, dtype, strides, dims, ghost, value_range, repeat, co
     return row
 
 
+def guided(a):
+    """the --guided run: the same field, model and seeds trained with error-guided and with uniform batches, side by side"""
+    dims = (a.size,) * 3
+    f = syn.analytic_volume(a.size)
+    f = (f - f.min()) / (f.max() - f.min())
+    field = api.DeviceArray.from_numpy(np.clip(np.float32(1.6) * f - np.float32(0.3), 0, 1).astype(np.float32))
+    before = os.environ.get("VNR_AMD_INIT_SEED")
+    os.environ["VNR_AMD_INIT_SEED"] = str(1000 + a.seed)      # both models start from the same parameters
+    runs = {}
+    for name in ("guided", "uniform"):
+        volume, _ = api.vnrCreateSimpleVolumeFromDevice(field.ptr, dims, np.float32, None, (0.0, 1.0))
+        neural = api.vnrCreateNeuralVolume(syn.model_config(n_levels=8, n_features=8, log2_hashmap_size=15, base_resolution=16), volume)
+        api.check(api.lib().vnrAmdNeuralVolumeSetSamplerSeed(neural.h, a.seed, 1))
+        runs[name] = (volume, neural)
+    if before is None:
+        os.environ.pop("VNR_AMD_INIT_SEED", None)
+    else:
+        os.environ["VNR_AMD_INIT_SEED"] = before
+    print(f"library build {api.lib().vnrAmdBuildId().decode()}; --guided: {a.size}^3 float32 blob field, {a.steps_per_frame} steps, "
+          f"refresh every {a.refresh_every}, uniform fraction {a.uniform_fraction}")
+    done = 0
+    while done < a.steps_per_frame:
+        steps = min(a.refresh_every, a.steps_per_frame - done)
+        row = {"steps": done + steps}
+        for name, (volume, neural) in runs.items():
+            t0 = time.perf_counter()
+            api.vnrNeuralVolumeTrain(neural, steps, True)
+            api.check(api.lib().vnrAmdSynchronize())
+            row[name + "_train_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
+            t0 = time.perf_counter()
+            if name == "guided":     # the report and the new weight map in one call
+                rep = api.neural_volume_guide_sampling_by_error(neural, a.uniform_fraction)
+            else:
+                rep = api.vnrNeuralVolumeErrorAgainstDevice(neural, api.lib().vnrAmdSimpleVolumeDeviceData(volume.h), np.float32)
+            row[name + "_report_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
+            row[name + "_max_abs_error"] = rep["max_abs"]
+            row[name + "_psnr_db"] = round(rep["psnr_db"], 3)
+        done += steps
+        print(json.dumps(row))
+    field.free()
+    return 0
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description="in-situ training of a time series from device memory")
     p.add_argument("--size", type=int, default=64)
@@ -117,13 +166,20 @@ def main(argv=None):
     p.add_argument("--repeat", type=int, default=5)
     p.add_argument("--compare-host", action="store_true")
     p.add_argument("--round-trip", action="store_true")
+    p.add_argument("--guided", action="store_true")
+    p.add_argument("--uniform-fraction", type=float, default=0.25)
+    p.add_argument("--refresh-every", type=int, default=100)
     p.add_argument("--seed", type=int, default=1)
     a = p.parse_args(argv)
+    if a.guided and (a.steps_per_frame <= 0 or a.refresh_every <= 0 or not 0.0 <= a.uniform_fraction <= 1.0):
+        p.error("--guided needs --steps-per-frame > 0, --refresh-every > 0 and --uniform-fraction in [0, 1]")
     if a.round_trip and not a.steps_per_frame:
         p.error("--round-trip needs a trained network: --steps-per-frame > 0")
 
     api._lib.require_device()
     api.check(api.lib().vnrAmdInit(-1))
+    if a.guided:
+        return guided(a)
     dtype = np.dtype(a.dtype)
     dims = (a.size,) * 3
     n = a.size ** 3

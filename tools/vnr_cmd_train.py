@@ -10,6 +10,10 @@
   --quiet                    quiet mode
   --train-macrocell          train the macrocell grid at the same time
   --deterministic            bit-reproducible training (new: vnrAmdNeuralVolumeSetDeterministicTraining; not over RCCL)
+  --guided-every <int>       error-guided batches (new: vnrAmdNeuralVolumeGuideSamplingByError): every <int> steps the error of
+                             the network against the ground truth, per macrocell, becomes the weight map the next batches are
+                             drawn from; 0 = uniform batches, training mode GPU only                                           [0]
+  --uniform-fraction <float> the share of every guided batch that stays uniform over the volume                    [0.25]
 
 Like the reference it trains in bursts of 10 steps in fast mode, restarts when the loss is still > 0.9 after 5000 steps, prints
 the Summary block (STEP / LOSS / TIME / PSNR / SSIM) and writes ./params.json (BSON).
@@ -39,7 +43,14 @@ def main(argv=None):
     p.add_argument("--train-macrocell", action="store_true", help="train the macrocell grid at the same time")
     p.add_argument("--deterministic", action="store_true",
                    help="bit-reproducible training: the hash-grid gradient is summed in 64-bit fixed point (slower; not over RCCL)")
+    p.add_argument("--guided-every", type=int, default=0, metavar="int",
+                   help="error-guided batches: re-install the per-macrocell error map as sampling weights every <int> steps (0: uniform batches)")
+    p.add_argument("--uniform-fraction", type=float, default=0.25, metavar="float", help="the share of a guided batch that stays uniform")
     a = p.parse_args(argv)
+    if a.guided_every < 0 or not 0.0 <= a.uniform_fraction <= 1.0:
+        p.error("--guided-every must be >= 0 and --uniform-fraction must lie in [0, 1]")
+    if a.guided_every and a.training_mode != "GPU":
+        p.error("--guided-every needs the resident ground truth of training mode GPU")
 
     ctx = dist.init_from_env()        # one rank: binds the GPU; more: meets the other ranks (RCCL)
     root = ctx.rank == 0
@@ -68,6 +79,9 @@ def main(argv=None):
                 print(f"\r[train] {100.0 * i / max(a.max_num_steps, 1):5.1f} %  LOSS {loss:f}", end="", flush=True)
             if ctx.distributed:   # every rank takes the same decision: the largest loss any of them sees
                 loss = dist.all_reduce_host([loss], dist.MAX)[0]
+            # every rank computes the same map from identical replicas and the same ground truth, so all install the same weights
+            if a.guided_every and (i + 10) // a.guided_every > i // a.guided_every and i + 10 < a.max_num_steps:
+                api.neural_volume_guide_sampling_by_error(neural_volume, a.uniform_fraction)
             if i >= 5000 and loss > 0.9:   # bad loss (batch_trainer.cpp:108-112)
                 if root:
                     print("\nbad setup, ... restart")
@@ -75,6 +89,8 @@ def main(argv=None):
                 break
         if report:
             report.close()
+        if a.guided_every:   # the ground truth is shared by a restarted model and by the evaluation below: back to uniform batches
+            api.simple_volume_set_sampling_weights(simple_volume, None)
         if not restart:
             break
     if root and not a.quiet:

@@ -361,7 +361,8 @@ int    vnrAmdNeuralVolumeForwardBackward(vnrAmdVolume, size_t n, const float* d_
 /* Inspection of the last ForwardBackward / TrainBegin (tests/diag/grad_hammer.py; passive: no other call depends on them).
  * TrainingBuffer: device pointer + size of 0 the fp16 gradient blob, 1 dL/dfeatures [n][padded_width] fp16, 2 the encoded features,
  * 3 the hidden activations, 4 the int64 image of the grid part that deterministic training sums into (zero between steps; 0 bytes before the
- * first deterministic step).  RescatterGridGradients: clears the hash-grid part of the blob and repeats the grid backward alone on the
+ * first deterministic step), 5 dL/d(pre-activation) of every hidden layer's output [n_hidden_layers][n][n_neurons] fp16, 6 the loss-scaled
+ * dL/dy [n] fp16 after the output activation's backward, 7 the training forward's output [n] fp32.  RescatterGridGradients: clears the hash-grid part of the blob and repeats the grid backward alone on the
  * stored dL/dfeatures (same d_coords as the ForwardBackward it repeats).  GradientDistance: out4 = {sum (g - ref)^2, sum ref^2} over
  * the MLP part, then over the grid part, against an fp16 reference blob on the device, reduced on the device on the training stream. */
 int    vnrAmdNeuralVolumeTrainingBuffer(vnrAmdVolume, int which, const void** d_ptr, size_t* bytes);

@@ -924,6 +924,19 @@ def neural_gradients(v):
     return out
 
 
+def neural_training_buffer(v, which, dtype=np.float16):
+    """what the last ForwardBackward / TrainBegin kept on the device (vnrAmdNeuralVolumeTrainingBuffer: 0 the fp16 gradient blob, 1 dL/dfeatures,
+    2 features, 3 hidden activations, 4 the deterministic int64 image, 5 dL/d(pre-activation) of every hidden layer, 6 dL/dy, 7 the fp32 output),
+    downloaded as a flat array of `dtype`"""
+    p, n = C.c_void_p(), C.c_size_t()
+    check(lib().vnrAmdNeuralVolumeTrainingBuffer(v.h, int(which), C.byref(p), C.byref(n)))
+    check(lib().vnrAmdSynchronize())
+    out = np.empty(n.value // np.dtype(dtype).itemsize, dtype)
+    if n.value:
+        check(lib().vnrAmdMemcpyD2H(out.ctypes.data_as(C.c_void_p), p, n.value))
+    return out
+
+
 def neural_train_begin(v):
     check(lib().vnrAmdNeuralVolumeTrainBegin(v.h))
 

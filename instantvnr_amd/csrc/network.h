@@ -202,7 +202,8 @@ public:
   size_t level_range_hi(uint32_t level_end) const { return n_mlp_ + ((size_t)grid_.levels[level_end - 1].offset + grid_.levels[level_end - 1].size) * cfg_.n_features; }
   // Diagnostics of the training step (tests/diag/grad_hammer.py; passive: nothing else depends on them).  training_buffer: device
   // pointer and size of 0 the fp16 gradient blob, 1 dL/dfeatures [n][padded_width] fp16, 2 the features, 3 the hidden activations
-  // of the last forward_backward, 4 the deterministic mode's int64 image of the grid part.  rescatter_grid_gradients: clears the grid part of the blob and repeats step 5 alone on the stored
+  // of the last forward_backward, 4 the deterministic mode's int64 image of the grid part,
+  // 5 dL/d(pre-activation) of every hidden layer [(nh+1)][n][W] fp16, 6 the loss-scaled dL/dy [n] fp16, 7 the training forward's output [n] fp32.  rescatter_grid_gradients: clears the grid part of the blob and repeats step 5 alone on the stored
   // dL/dfeatures.  gradient_distance: {sum (g - ref)^2, sum ref^2} of the MLP part and of the grid part against an fp16 reference blob,
   // reduced on the device on stream s (what the blob holds BEFORE any download).
   const void* training_buffer(int which, size_t* bytes) const;

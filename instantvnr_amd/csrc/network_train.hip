@@ -1505,7 +1505,12 @@ const void* Network::training_buffer(int which, size_t* bytes) const
     *bytes = ts.grid_grads_i64.bytes();
     return ts.grid_grads_i64.ptr;
   }
-  default: throw std::runtime_error("training_buffer: 0 gradients, 1 dL/dfeatures, 2 features, 3 activations, 4 the deterministic int64 image");
+  // the MLP backward's own intermediates (tests/test_gpu_mlp_stages.py holds every stage of the step to the inputs it read)
+  case 5: { const TrainScratch& ts = scratch_of(this); *bytes = ts.d_all.bytes(); return ts.d_all.ptr; }
+  case 6: { const TrainScratch& ts = scratch_of(this); *bytes = ts.dy.bytes(); return ts.dy.ptr; }
+  case 7: { const TrainScratch& ts = scratch_of(this); *bytes = ts.y.bytes(); return ts.y.ptr; }
+  default: throw std::runtime_error("training_buffer: 0 gradients, 1 dL/dfeatures, 2 features, 3 activations, 4 the deterministic int64 image, "
+                                    "5 dL/d(pre-activation) of every hidden layer, 6 dL/dy, 7 the training forward's output");
   }
 }
 

@@ -98,13 +98,7 @@ class Case:
         api.check(L_.vnrAmdNeuralVolumeForwardBackward(vol.h, self.B, self.d_tc.ptr, self.d_tt.ptr))
 
     def buffer(self, vol, which):
-        p, n = C.c_void_p(), C.c_size_t()
-        api.check(L_.vnrAmdNeuralVolumeTrainingBuffer(vol.h, which, C.byref(p), C.byref(n)))
-        api.check(L_.vnrAmdSynchronize())
-        out = np.empty(n.value // 2, np.uint16)
-        if n.value:
-            api.check(L_.vnrAmdMemcpyD2H(out.ctypes.data_as(C.c_void_p), p, n.value))
-        return out
+        return api.neural_training_buffer(vol, which, np.uint16)
 
     def adopt_reference(self, vol):
         self.ref_host = self.buffer(vol, 0)

@@ -80,16 +80,8 @@ for i in range(max(want_idx) + 1):
                      gl[np.argmax(np.abs(gl - wl_))], wl_[np.argmax(np.abs(gl - wl_))], xl[np.argmax(np.abs(gl - wl_))]))
         if deep == 1e-5:
             # the forward activations and dL/dfeatures the library kept (vnrAmdNeuralVolumeTrainingBuffer), sample by sample against the restatement's
-            import ctypes as C
-            Lb = api.lib()
-
             def buf(which):
-                pp, nn = C.c_void_p(), C.c_size_t()
-                api.check(Lb.vnrAmdNeuralVolumeTrainingBuffer(vol.h, which, C.byref(pp), C.byref(nn)))
-                api.check(Lb.vnrAmdSynchronize())
-                out = np.empty(nn.value // 2, np.float16)
-                api.check(Lb.vnrAmdMemcpyD2H(out.ctypes.data_as(C.c_void_p), pp, nn.value))
-                return out
+                return api.neural_training_buffer(vol, which, np.float16)
             nh = H - 1
             feat = o.grid_encode(ocfg, params[n_mlp:].view(np.uint16), tc)
             _, acts_o = o.mlp_forward(params[:n_mlp].view(np.uint16), in_w, W, nh, feat, activation=code, want_activations=True)

@@ -8,7 +8,6 @@ oracle.train_oracle.corner_indices_and_weights.  Per entry the deterministic res
 
 of fp16(exact): one rounding of the sum to half, one rounding per fixed-point term (e = floor(62 - log2(8 n M)), M = max |dL/dfeature| over
 the batch and the active levels' columns), and the fp32 rounding of each product w * g (which matters only where terms cancel)."""
-import ctypes as C
 import math
 import os
 import socket
@@ -33,14 +32,7 @@ def _mode_default_off(monkeypatch):
     monkeypatch.delenv("VNR_AMD_TRAIN_OVERLAP", raising=False)
 
 
-def training_buffer(vol, which, dtype):
-    p, n = C.c_void_p(), C.c_size_t()
-    api.check(api.lib().vnrAmdNeuralVolumeTrainingBuffer(vol.h, which, C.byref(p), C.byref(n)))
-    api.check(api.lib().vnrAmdSynchronize())
-    out = np.empty(n.value // np.dtype(dtype).itemsize, dtype)
-    if n.value:
-        api.check(api.lib().vnrAmdMemcpyD2H(out.ctypes.data_as(C.c_void_p), p, n.value))
-    return out
+training_buffer = api.neural_training_buffer          # (vol, which, dtype) -> what the last ForwardBackward kept, downloaded
 
 
 def blob(vol):

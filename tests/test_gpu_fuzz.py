@@ -270,16 +270,10 @@ def grid_gradient_post_mortem(vol, tc, grads, w_all, ref, n_mlp, d):
     the blob downloaded again (a download that raced the stream), dL/dfeatures against the restatement's (the MLP backward's side), the
     grid backward alone repeated on the stored dL/dfeatures (a scatter that lost or double-counted updates).  Printed, and kept in
     gpurun_out/ as an .npz"""
-    import ctypes as C
     L = api.lib()
 
     def buf(which):
-        p, n = C.c_void_p(), C.c_size_t()
-        api.check(L.vnrAmdNeuralVolumeTrainingBuffer(vol.h, which, C.byref(p), C.byref(n)))
-        api.check(L.vnrAmdSynchronize())
-        out = np.empty(n.value // 2, np.float16)
-        api.check(L.vnrAmdMemcpyD2H(out.ctypes.data_as(C.c_void_p), p, n.value))
-        return out
+        return api.neural_training_buffer(vol, which, np.float16)
 
     w = w_all[n_mlp:]
     again = buf(0).astype(np.float64)

@@ -288,6 +288,62 @@ int    vnrAmdNeuralVolumeDecodeToDevice(vnrAmdVolume neural, void* d_out, int va
 int    vnrAmdNeuralVolumeErrorAgainstDevice(vnrAmdVolume neural, const void* d_ref, int value_type, const int64_t strides[3],
                                             const int box_lo[3], const int box_size[3], float range_lo, float range_hi,
                                             void* stream, vnrAmdDecodeError* out, float* d_block_max);
+/* AMD extension: error-bounded round trip.  BuildCorrection stores what the network missed: quantised residuals for exactly the
+ * macrocells (16^3, the grid of vnrAmdVolumeGetMacrocell, ragged at the upper faces) in which some voxel of the whole-grid decode
+ * misses the tolerance eps against the field d_ref; DecodeToDeviceCorrected decodes with that applied.  The pair (params.json,
+ * serialised correction) is the compressed field.  The box is always the whole grid of the volume; pointer, strides, alignment,
+ * allocation room, stream and value range are those of DecodeToDevice, with its refusals and messages.
+ *
+ * Per voxel, dec is the typed value DecodeToDevice stores for this value type and range, ref the voxel of d_ref, eps a finite
+ * double >= 0 in data units.  Every step is an integer operation or one IEEE double operation:
+ *   kind 0, the integer types:  E = floor(min(eps, 2^40)) (no voxel of a 32-bit type can miss 2^32), s = 2 E + 1,
+ *       r = (int64)ref - (int64)dec, q = floor_div(r + E, s), corrected = clamp(dec + q s, Tmin, Tmax) in int64.
+ *       |corrected - ref| <= E <= eps for every voxel, and q == 0 exactly where |r| <= E.
+ *   kind 1, FLOAT / DOUBLE with eps > 0:  s = 2 eps in double, r = (double)ref - (double)dec, q = rint(r / s) (one division, ties
+ *       to even), corrected = (T)__dadd_rn((double)dec, __dmul_rn((double)q, s)), never an fma; a voxel with q == 0 keeps dec bit
+ *       for bit.  A voxel whose r is a NaN (a NaN in ref or dec, two infinities of one sign) gets q = 0, is counted in n_nan and
+ *       stays as decoded.  |corrected - ref| <= eps + 2^-50 (|ref| + |dec| + eps) + ulp_T(corrected) / 2: the roundings of r, r / s
+ *       and q s can put a voxel a few last bits over eps itself, which is why max_abs_after is reported exactly.
+ *   kind 2, FLOAT / DOUBLE with eps == 0, verbatim:  a voxel differs where the bit patterns of dec and ref differ; the code of
+ *       every voxel of a flagged cell is ref's bit pattern and corrected = ref bit for bit, NaN payloads and -0.0 included.
+ * A cell is flagged iff some voxel in it has q != 0 (kind 2: differs).  With m = max |q| over the cell its codes are 1 byte wide
+ * if m <= 127, 2 if m <= 32767, 4 otherwise, little-endian signed (kind 2: sizeof(T)); m > 2^31 - 1 in any cell refuses the build.
+ * The codes of a flagged cell cover all its voxels (0 within tolerance) in the order lx + cx (ly + cy lz), cx = min(16, dims.x -
+ * 16 ix) and likewise cy, cz; each cell's codes are padded with zero bytes to a multiple of 16 bytes; cells in ascending index.
+ *
+ * Serialised form, little-endian: a header of 104 bytes, n_flagged entries {uint32 cell, uint32 width}, the payload.  Header:
+ *   char[8] "VNRCORR1" | uint32 version = 1 | uint32 value_type | int32 dims[3] | uint32 n_flagged | double eps | float range_lo,
+ *   range_hi | uint32 kind | uint32 reserved = 0 | uint64 step (kind 0: s; kind 1: the bits of the double s; kind 2: 0) |
+ *   uint64 params_hash | uint64 n_params | uint64 payload_bytes | double max_abs_after | uint64 reserved = 0
+ * params_hash: FNV-1a 64 of the bytes vnrAmdNeuralVolumeGetParamsFP16 returns at build time.  CreateCorrectionFromBytes is host
+ * code (no device needed; the device copy is made at the first apply) and refuses, by name, anything but a well-formed blob:
+ * magic, version, value type, positive dims, n_flagged <= cells, cells strictly ascending and in range, a width legal for kind
+ * and type, kind / step / eps consistent, reserved fields zero, payload_bytes = the sum of the padded cell sizes, the exact size.
+ *
+ * Info: n_voxels_flagged = voxels with q != 0 (kind 2: that differ); max_abs_before / max_abs_after = max |(double)dec - (double)
+ * ref| and max |(double)corrected - (double)ref| over all voxels, exact (NaN differences aside; NaN if there is no other voxel);
+ * worst_after = the voxel of max_abs_after, the lowest x-fastest index among equals.  A correction loaded from bytes reports
+ * max_abs_before = NaN, worst_after = -1, -1, -1, n_nan = n_voxels_flagged = 0 and max_abs_after from the header.
+ * The build evaluates the network twice, chunk by chunk (VNR_AMD_DECODE_CHUNK, as above; the result does not depend on it), and
+ * keeps no full-size intermediate.  The apply writes nothing but the volume's voxels: ghost layers keep their bytes.
+ * verify_params != 0 hashes the volume's current parameters and refuses when hash or count differ from the correction's; with 0
+ * the caller vouches that the parameters are the ones the correction was built on.
+ *
+ * Errors (NULL / VNR_AMD_ERROR and a message; nothing has been written): those of DecodeToDevice; eps negative, NaN or infinite;
+ * a cell that needs codes wider than 32 bits; a correction whose dims differ from the volume's; a null handle; malformed bytes. */
+typedef struct vnrAmdCorrection_t* vnrAmdCorrection;
+typedef struct vnrAmdCorrectionInfo {
+  int dims[3], value_type, kind; double eps; float range_lo, range_hi;
+  uint64_t n_cells, n_flagged, n_voxels_flagged, payload_bytes, serialized_bytes, n_nan, params_hash, n_params;
+  double max_abs_before, max_abs_after; int worst_after[3]; } vnrAmdCorrectionInfo;
+vnrAmdCorrection vnrAmdNeuralVolumeBuildCorrection(vnrAmdVolume neural, const void* d_ref, int value_type, const int64_t strides[3],
+                                                   float range_lo, float range_hi, double eps, void* stream);
+int  vnrAmdCorrectionGetInfo(vnrAmdCorrection, vnrAmdCorrectionInfo*);
+int  vnrAmdCorrectionSerialize(vnrAmdCorrection, void** bytes, size_t* size);          /* vnrAmdFreeHost */
+vnrAmdCorrection vnrAmdCreateCorrectionFromBytes(const void* bytes, size_t size);      /* host only; uploaded at first use */
+int  vnrAmdNeuralVolumeDecodeToDeviceCorrected(vnrAmdVolume neural, vnrAmdCorrection, void* d_out, const int64_t strides[3],
+                                               void* stream, int verify_params);
+void vnrAmdReleaseCorrection(vnrAmdCorrection);
 /* hash-grid encode only (tcnn_impl_decoder.cu:177-230, column = level*F + f): fp16 [n][padded_width] */
 int    vnrAmdNeuralVolumeEncode(vnrAmdVolume, size_t n, const float* d_coords, uint16_t* d_features, void* stream);
 /* AMD extension: state of the brick image, the de-hashed inference copy of the hashed levels (csrc/network.h).  It is built

@@ -56,6 +56,13 @@ class DecodeError(C.Structure):
                 ("psnr_db", C.c_double)]
 
 
+class CorrectionInfo(C.Structure):
+    _fields_ = [("dims", C.c_int * 3), ("value_type", C.c_int), ("kind", C.c_int), ("eps", C.c_double), ("range_lo", C.c_float), ("range_hi", C.c_float),
+                ("n_cells", C.c_uint64), ("n_flagged", C.c_uint64), ("n_voxels_flagged", C.c_uint64), ("payload_bytes", C.c_uint64),
+                ("serialized_bytes", C.c_uint64), ("n_nan", C.c_uint64), ("params_hash", C.c_uint64), ("n_params", C.c_uint64),
+                ("max_abs_before", C.c_double), ("max_abs_after", C.c_double), ("worst_after", C.c_int * 3)]
+
+
 def declared_symbols():
     """every function name declared in include/vnr_amd.h"""
     text = open(HEADER).read()
@@ -244,6 +251,12 @@ def lib():
     sig("vnrAmdSimpleVolumeSamplingCdf", P, P)
     sig("vnrAmdSimpleVolumeTakeSamplesWeighted", I, P, SZ, P, P, P)
     sig("vnrAmdNeuralVolumeGuideSamplingByError", I, P, F, C.POINTER(DecodeError))
+    sig("vnrAmdNeuralVolumeBuildCorrection", P, P, P, I, I64P, F, F, D, P)
+    sig("vnrAmdCorrectionGetInfo", I, P, C.POINTER(CorrectionInfo))
+    sig("vnrAmdCorrectionSerialize", I, P, C.POINTER(P), C.POINTER(SZ))
+    sig("vnrAmdCreateCorrectionFromBytes", P, P, SZ)
+    sig("vnrAmdNeuralVolumeDecodeToDeviceCorrected", I, P, P, P, I64P, P, I)
+    sig("vnrAmdReleaseCorrection", None, P)
     _lib = L
     return L
 

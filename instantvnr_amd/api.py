@@ -509,6 +509,57 @@ def vnrNeuralVolumeErrorAgainstDevice(v, d_ptr, dtype, strides=None, box=None, v
     return out
 
 
+class Correction(_Handle):
+    """an error-bound correction (include/vnr_amd.h, "error-bounded round trip"): built by vnrNeuralVolumeBuildCorrection or loaded
+    with Correction.from_bytes; to_bytes() beside params.json is the compressed field"""
+    _release = "vnrAmdReleaseCorrection"
+
+    def info(self):
+        """-> dict of vnrAmdCorrectionInfo; dims and worst_after as (x, y, z)"""
+        e = _lib.CorrectionInfo()
+        check(lib().vnrAmdCorrectionGetInfo(self.h, C.byref(e)))
+        out = {k: getattr(e, k) for k, _ in _lib.CorrectionInfo._fields_}
+        out["dims"], out["worst_after"] = tuple(e.dims), tuple(e.worst_after)
+        return out
+
+    def to_bytes(self):
+        out = C.c_void_p()
+        n = C.c_size_t()
+        check(lib().vnrAmdCorrectionSerialize(self.h, C.byref(out), C.byref(n)))
+        b = C.string_at(out, n.value)
+        lib().vnrAmdFreeHost(out)
+        return b
+
+    @classmethod
+    def from_bytes(cls, b):
+        """host only: the bytes are validated here, the device copy is made by the first apply"""
+        b = bytes(b)
+        return cls(lib().vnrAmdCreateCorrectionFromBytes(b, len(b)))
+
+
+def vnrNeuralVolumeBuildCorrection(v, d_ref, dtype, eps, strides=None, value_range=None, stream=None):
+    """residual corrections for the macrocells where what vnrNeuralVolumeDecodeToDevice would store (same dtype and value_range, the
+    whole grid) misses `eps` (data units, >= 0) against the field at `d_ref` -> Correction"""
+    p, _, t, s, _, _, st = _device_source_args(d_ref, dtype, strides, None, stream)
+    lo, hi = _round_trip_range(np.dtype(dtype), value_range)
+    return Correction(lib().vnrAmdNeuralVolumeBuildCorrection(v.h, p, t, s, lo, hi, float(eps), st))
+
+
+def vnrNeuralVolumeDecodeToDeviceCorrected(v, correction, d_ptr, strides=None, stream=None, verify_params=False):
+    """vnrNeuralVolumeDecodeToDevice of the whole grid with `correction` applied; value type and range are the correction's.
+    verify_params: refuse unless the volume's parameters hash to what the correction was built on."""
+    ptr = d_ptr.ptr if isinstance(d_ptr, DeviceArray) else d_ptr
+    if not ptr:
+        raise VnrAmdError("null device data")
+    s = None
+    if strides is not None:
+        sl = [int(x) for x in np.atleast_1d(strides)]
+        if len(sl) != 3 or min(sl) <= 0:
+            raise VnrAmdError(f"strides must be three positive element strides (sx, sy, sz), got {strides!r}")
+        s = (C.c_int64 * 3)(*sl)
+    check(lib().vnrAmdNeuralVolumeDecodeToDeviceCorrected(v.h, correction.h, C.c_void_p(ptr), s, C.c_void_p(stream) if stream else None, int(bool(verify_params))))
+
+
 def vnrNeuralVolumeSerializeParams(v, filename=None):
     """with a filename: writes BSON params.json; without: returns the BSON bytes"""
     if filename is not None:

@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <cstdio>
 #include <fstream>
+#include <limits>
 #include <memory>
 
 #include "dist.h"
@@ -17,6 +18,7 @@ struct vnrAmdVolume_t { std::shared_ptr<VolumeBase> v; };
 struct vnrAmdRenderer_t { std::unique_ptr<Renderer> r; std::shared_ptr<VolumeBase> volume; };
 struct vnrAmdTransferFunction_t { TransferFunctionData d; };
 struct vnrAmdCamera_t { CameraData d; };
+struct vnrAmdCorrection_t { std::shared_ptr<Correction> c; };
 
 namespace {
 thread_local std::string g_last_error;
@@ -71,6 +73,11 @@ SimpleVolume* as_simple(vnrAmdVolume v)
   if (!v || !v->v) throw std::runtime_error("null volume");
   if (v->v->is_network()) throw std::runtime_error("expecting a simple volume");  // api.cpp:128-130
   return static_cast<SimpleVolume*>(v->v.get());
+}
+Correction* as_correction(vnrAmdCorrection c)
+{
+  if (!c || !c->c) throw std::runtime_error("null correction");
+  return c->c.get();
 }
 void* dup_bytes(const void* p, size_t n)
 {
@@ -588,6 +595,55 @@ int vnrAmdNeuralVolumeErrorAgainstDevice(vnrAmdVolume v, const void* d_ref, int 
                                        reinterpret_cast<DecodeError*>(out), d_block_max);
   });
 }
+vnrAmdCorrection vnrAmdNeuralVolumeBuildCorrection(vnrAmdVolume v, const void* d_ref, int value_type, const int64_t strides[3], float range_lo, float range_hi,
+                                                   double eps, void* stream)
+{
+  return guarded_new<vnrAmdCorrection_t>([&]() {
+    return new vnrAmdCorrection_t{as_neural(v)->build_correction(DeviceSource{d_ref, value_type, strides, (hipStream_t)stream}, range_lo, range_hi, eps)};
+  });
+}
+int vnrAmdCorrectionGetInfo(vnrAmdCorrection c, vnrAmdCorrectionInfo* out)
+{
+  return guarded([&]() {
+    const Correction* k = as_correction(c);
+    if (!out) throw std::runtime_error("null result");
+    const CorrectionHeader& h = k->data.h;
+    *out = vnrAmdCorrectionInfo{};
+    for (int a = 0; a < 3; ++a) { out->dims[a] = h.dims[a]; out->worst_after[a] = k->worst_after[a]; }
+    out->value_type = h.value_type; out->kind = (int)h.kind; out->eps = h.eps; out->range_lo = h.range_lo; out->range_hi = h.range_hi;
+    out->n_cells = correction_n_cells(h.dims); out->n_flagged = k->data.cells.size(); out->n_voxels_flagged = k->n_voxels_flagged;
+    out->payload_bytes = k->data.payload.size(); out->serialized_bytes = correction_serialized_bytes(k->data); out->n_nan = k->n_nan;
+    out->params_hash = h.params_hash; out->n_params = h.n_params; out->max_abs_before = k->max_abs_before; out->max_abs_after = h.max_abs_after;
+  });
+}
+int vnrAmdCorrectionSerialize(vnrAmdCorrection c, void** bytes, size_t* size)
+{
+  return guarded([&]() {
+    const Correction* k = as_correction(c);
+    if (!bytes || !size) throw std::runtime_error("null result");
+    const std::vector<uint8_t> b = correction_write(k->data);
+    *bytes = dup_bytes(b.data(), b.size());
+    *size = b.size();
+  });
+}
+vnrAmdCorrection vnrAmdCreateCorrectionFromBytes(const void* bytes, size_t size)
+{
+  return guarded_new<vnrAmdCorrection_t>([&]() {
+    auto k = std::make_shared<Correction>();
+    k->data = correction_parse(bytes, size);
+    k->max_abs_before = std::numeric_limits<double>::quiet_NaN();   // known to the build alone; worst_after = -1, -1, -1 and the counts 0 likewise
+    return new vnrAmdCorrection_t{std::move(k)};
+  });
+}
+int vnrAmdNeuralVolumeDecodeToDeviceCorrected(vnrAmdVolume v, vnrAmdCorrection c, void* d_out, const int64_t strides[3], void* stream, int verify_params)
+{
+  return guarded([&]() {
+    NeuralVolume* n = as_neural(v);
+    Correction* k = as_correction(c);
+    n->decode_to_device_corrected(*k, DeviceTarget{d_out, k->data.h.value_type, strides, (hipStream_t)stream}, verify_params != 0);
+  });
+}
+void vnrAmdReleaseCorrection(vnrAmdCorrection c) { delete c; }
 int vnrAmdNeuralVolumeSerializeParamsToFile(vnrAmdVolume v, const char* filename)
 {
   return guarded([&]() {

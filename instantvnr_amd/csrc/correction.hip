@@ -1,0 +1,763 @@
+// correction.hip — error-bounded round trip: residual corrections for the macrocells where the decode misses a tolerance, and the
+// decode with a correction applied.  The last step of the in-situ loop of ingest.hip / decode.hip / guided_sampler.hip.
+//
+// build_correction walks the whole grid twice in chunks of linear voxel indices, exactly as decode.hip's error report does (the same
+// VNR_AMD_DECODE_CHUNK, scratch and decode_chunk; the walker, the conversion and the validation below are copies of decode.hip's,
+// which keeps its own): pass 1 reduces max |q| per macrocell (one atomicMax per cell change of a lane) and the error before; the host
+// turns the cell map into per-cell {payload offset, code width}; pass 2 evaluates the network again, stores every voxel's code of
+// the flagged cells with one plain store each and reduces the error after.  The apply kernel decodes, looks the voxel's cell up and
+// stores the corrected value in the decode's 16-byte pieces.  The arithmetic is integer or single IEEE double operations
+// (include/vnr_amd.h spells it out); tests/error_bound_ref.py restates it in numpy and is matched bit for bit.
+#include "volume.h"
+
+#include <algorithm>
+#include <cstdlib>
+#include <limits>
+#include <type_traits>
+
+namespace vnr {
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr uint64_t kDefaultChunk = 1ull << 22, kMaxChunk = 1ull << 28;   // decode.hip's
+
+// ---- decode.hip's walk of the caller's array ---------------------------------------------------------------------------------------------
+// runs of run_len contiguous elements; run r starts at element (r % runs_y) * sy + (r / runs_y) * sz and holds the box's linear indices
+// [r * run_len, (r + 1) * run_len).  sx != 1: no runs, one voxel at a time.
+struct BoxLayout {
+  uint64_t bx, by, bz;
+  int64_t sx, sy, sz;
+  uint64_t run_len, runs_y;
+  bool gather;
+};
+
+template <typename T> struct PieceOf { static constexpr int n = 16 / (int)sizeof(T); };
+
+// For the linear box indices [b, e): f.piece(T* p, i) for every whole 16-byte piece (p 16-byte aligned, N voxels from index i on)
+// and f.one(T* p, i) for every other voxel.  T is const-qualified for a source.
+template <typename T, typename F>
+__device__ __forceinline__ void for_each_chunk_voxel(T* base, const BoxLayout& L, uint64_t b, uint64_t e, F& f)
+{
+  constexpr int N = PieceOf<std::remove_const_t<T>>::n;
+  if (L.gather) {
+    for (uint64_t i = b + (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < e; i += (uint64_t)gridDim.x * kBlock) {
+      const uint64_t x = i % L.bx, yz = i / L.bx, y = yz % L.by, z = yz / L.by;
+      f.one(base + ((int64_t)x * L.sx + (int64_t)y * L.sy + (int64_t)z * L.sz), i);
+    }
+    return;
+  }
+  const uint64_t r0 = b / L.run_len, r1 = (e - 1) / L.run_len;   // the runs this chunk touches
+  // per run: 1 (the head) + the 16-byte pieces that cover the longest part a run can have inside this chunk
+  const uint64_t P = 1 + (std::min(L.run_len, e - b) + N - 1) / N, work = (r1 - r0 + 1) * P;
+  for (uint64_t g = (uint64_t)blockIdx.x * kBlock + threadIdx.x; g < work; g += (uint64_t)gridDim.x * kBlock) {
+    uint64_t r, p;
+    if (work <= 0xffffffffull) { const uint32_t q = (uint32_t)g / (uint32_t)P; r = r0 + q; p = (uint32_t)g - q * (uint32_t)P; }
+    else { const uint64_t q = g / P; r = r0 + q; p = g - q * P; }
+    const uint64_t run_first = r * L.run_len;
+    const uint64_t lo = std::max(b, run_first), hi = std::min(e, run_first + L.run_len);   // the run's part inside the chunk
+    const uint64_t len = hi - lo;
+    uint64_t ry, rz;
+    if (r <= 0xffffffffull) { rz = (uint32_t)r / (uint32_t)L.runs_y; ry = (uint32_t)r - (uint32_t)rz * (uint32_t)L.runs_y; }
+    else { rz = r / L.runs_y; ry = r - rz * L.runs_y; }
+    T* part = base + ((int64_t)ry * L.sy + (int64_t)rz * L.sz + (int64_t)(lo - run_first));
+    // elements in front of the first 16-byte boundary of this part (the array is aligned to its element size)
+    const uint64_t head = std::min<uint64_t>(((16u - (uint32_t)((uintptr_t)part & 15u)) & 15u) / (uint32_t)sizeof(T), len);
+    if (p == 0) {
+      for (uint64_t k = 0; k < head; ++k) f.one(part + k, lo + k);
+      continue;
+    }
+    const uint64_t e0 = head + (p - 1) * N;
+    if (e0 >= len) continue;
+    if (e0 + N <= len) f.piece(part + e0, lo + e0);
+    else for (uint64_t k = e0; k < len; ++k) f.one(part + k, lo + k);
+  }
+}
+
+// ---- decode.hip's conversion: network output -> the typed voxel ------------------------------------------------------------------------
+struct Conversion {
+  float lo, width;   // d = v * width + lo, two roundings
+  bool scale;        // false: d = v
+};
+
+template <typename T>
+__device__ __forceinline__ T convert_value(float v, const Conversion& c)
+{
+  const float d = c.scale ? __fadd_rn(__fmul_rn(v, c.width), c.lo) : v;
+  if constexpr (std::is_same_v<T, float>) return d;
+  else if constexpr (std::is_same_v<T, double>) return (double)d;
+  else {
+    const double r = rint((double)d);   // ties to even
+    constexpr double tmin = (double)std::numeric_limits<T>::lowest(), tmax = (double)std::numeric_limits<T>::max();
+    if (r != r) return (T)0;
+    return r <= tmin ? std::numeric_limits<T>::lowest() : (r >= tmax ? std::numeric_limits<T>::max() : (T)r);
+  }
+}
+
+// ---- the quantiser (include/vnr_amd.h, "error-bounded round trip") ----------------------------------------------------------------------
+struct Quantiser {
+  uint32_t kind;
+  int64_t E, s;      // kind 0: floor(eps), 2 E + 1
+  int64_t qmax;      // kind 0: 2^34 / s + 1; a code beyond it saturates every type, so q is clamped to it before q * s (no overflow)
+  double sd;         // kind 1: 2 eps
+};
+
+template <typename T> struct BitsOf { using type = std::conditional_t<sizeof(T) == 8, uint64_t, uint32_t>; };
+
+template <typename T>
+__device__ __forceinline__ typename BitsOf<T>::type bits_of(T v)
+{
+  typename BitsOf<T>::type b;
+  __builtin_memcpy(&b, &v, sizeof(T));
+  return b;
+}
+
+// one voxel's code.  q: the signed code of kinds 0 and 1 (kind 2: 1 where the bit patterns differ); aq: |q| saturated to 32 bits;
+// nan: the difference is a NaN (a NaN in ref or dec, two infinities of one sign): q = 0, the voxel stays as decoded
+template <typename T>
+__device__ __forceinline__ void quantise(T dec, T ref, const Quantiser& k, int64_t& q, uint32_t& aq, bool& nan)
+{
+  nan = false;
+  if constexpr (std::is_floating_point_v<T>) {
+    const double r = __dsub_rn((double)ref, (double)dec);
+    nan = r != r;
+    if (k.kind == kCorrectionVerbatim) { q = bits_of(dec) != bits_of(ref) ? 1 : 0; aq = (uint32_t)q; return; }
+    const double qd = nan ? 0.0 : rint(__ddiv_rn(r, k.sd));   // one division, ties to even
+    const double a = fabs(qd);
+    if (a >= 4294967295.0) { aq = 0xffffffffu; q = qd < 0.0 ? -4294967295ll : 4294967295ll; }   // (the build is refused)
+    else { q = (int64_t)qd; aq = (uint32_t)a; }
+  } else {
+    const int64_t r = (int64_t)ref - (int64_t)dec, t = r + k.E;
+    if ((uint64_t)t <= (uint64_t)(2 * k.E)) { q = 0; aq = 0; return; }   // |r| <= E: the common case, no division
+    q = t / k.s;
+    if (t < 0 && q * k.s != t) --q;   // floor
+    const uint64_t a = (uint64_t)(q < 0 ? -q : q);
+    aq = a >= 0xffffffffull ? 0xffffffffu : (uint32_t)a;
+  }
+}
+
+// what the apply stores for a voxel of a flagged cell, from the decoded value and its code
+template <typename T>
+__device__ __forceinline__ T corrected_value(T dec, int64_t q, const Quantiser& k)
+{
+  if (q == 0) return dec;   // (dec + 0 * s, spelled as what it is: -0.0 and a NaN's payload stay)
+  if constexpr (std::is_floating_point_v<T>) {
+    return (T)__dadd_rn((double)dec, __dmul_rn((double)q, k.sd));   // never an fma
+  } else {
+    const int64_t v = (int64_t)dec + std::max(-k.qmax, std::min(k.qmax, q)) * k.s;
+    constexpr int64_t tmin = (int64_t)std::numeric_limits<T>::lowest(), tmax = (int64_t)std::numeric_limits<T>::max();
+    return (T)std::max(tmin, std::min(tmax, v));
+  }
+}
+
+// the macrocells of the grid and a voxel's place in its cell
+struct CellGrid {
+  uint32_t dx, dy, dz, mcx, mcy;
+  __device__ __forceinline__ uint32_t cell(uint32_t x, uint32_t y, uint32_t z) const { return (x >> 4) + mcx * ((y >> 4) + mcy * (z >> 4)); }
+  __device__ __forceinline__ uint32_t local(uint32_t x, uint32_t y, uint32_t z) const
+  {
+    const uint32_t cx = std::min(16u, dx - (x & ~15u)), cy = std::min(16u, dy - (y & ~15u));
+    return (x & 15u) + cx * ((y & 15u) + cy * (z & 15u));
+  }
+};
+
+__device__ __forceinline__ void split_index(uint64_t i, uint64_t bx, uint64_t by, uint32_t& x, uint32_t& y, uint32_t& z)
+{
+  const uint64_t yz = i / bx;
+  x = (uint32_t)(i - yz * bx); y = (uint32_t)(yz % by); z = (uint32_t)(yz / by);
+}
+
+template <typename T> struct alignas(16) Piece { T v[PieceOf<T>::n]; };
+
+// ---- reductions ---------------------------------------------------------------------------------------------------------------------------
+struct Partial {
+  double max_abs;      // -1: no voxel yet
+  uint64_t worst;      // the lowest linear index among equals
+  uint64_t n_a, n_b;   // pass 1: voxels over the tolerance, NaN voxels
+};
+
+__device__ __forceinline__ void block_reduce(double& mx, uint64_t& mi, uint64_t& na, uint64_t& nb)
+{
+  for (int off = 32; off > 0; off >>= 1) {
+    const double omx = __shfl_down(mx, off, 64);
+    const uint64_t omi = (uint64_t)__shfl_down((unsigned long long)mi, off, 64);
+    na += (uint64_t)__shfl_down((unsigned long long)na, off, 64);
+    nb += (uint64_t)__shfl_down((unsigned long long)nb, off, 64);
+    if (omx > mx || (omx == mx && omi < mi)) { mx = omx; mi = omi; }
+  }
+  __shared__ double w_mx[kBlock / 64];
+  __shared__ uint64_t w_mi[kBlock / 64], w_na[kBlock / 64], w_nb[kBlock / 64];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (lane == 0) { w_mx[wave] = mx; w_mi[wave] = mi; w_na[wave] = na; w_nb[wave] = nb; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < kBlock / 64; ++w) {
+      if (w_mx[w] > mx || (w_mx[w] == mx && w_mi[w] < mi)) { mx = w_mx[w]; mi = w_mi[w]; }
+      na += w_na[w]; nb += w_nb[w];
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) correction_init_kernel(Partial* __restrict__ partials, uint32_t n)
+{
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < n) partials[i] = Partial{-1.0, ~0ull, 0, 0};
+}
+
+__global__ void __launch_bounds__(kBlock) correction_final_kernel(const Partial* __restrict__ partials, uint32_t n, Partial* __restrict__ out)
+{
+  double mx = -1.0;
+  uint64_t mi = ~0ull, na = 0, nb = 0;
+  for (uint32_t i = threadIdx.x; i < n; i += kBlock) {
+    const Partial p = partials[i];
+    if (p.max_abs > mx || (p.max_abs == mx && p.worst < mi)) { mx = p.max_abs; mi = p.worst; }
+    na += p.n_a; nb += p.n_b;
+  }
+  block_reduce(mx, mi, na, nb);
+  if (threadIdx.x == 0) *out = Partial{mx, mi, na, nb};
+}
+
+__device__ __forceinline__ void merge_partial(Partial* __restrict__ partials, double mx, uint64_t mi, uint64_t na, uint64_t nb)
+{
+  // one partial per block; the launches of one pass run one behind the other on one stream, so block k owns partials[k] throughout
+  Partial p = partials[blockIdx.x];
+  if (mx > p.max_abs || (mx == p.max_abs && mi < p.worst)) { p.max_abs = mx; p.worst = mi; }
+  p.n_a += na; p.n_b += nb;
+  partials[blockIdx.x] = p;
+}
+
+// ---- pass 1: max |q| per cell, the error before ----------------------------------------------------------------------------------------------
+template <typename T>
+struct MeasureOp {
+  const float* __restrict__ values;   // values[i - b]
+  uint64_t b;
+  Conversion c;
+  Quantiser k;
+  uint64_t bx, by;
+  CellGrid g;
+  uint32_t* cells;
+  double mx = -1.0;
+  uint64_t mi = ~0ull, n_over = 0, n_nan = 0;
+  uint32_t cell = 0xffffffffu, cell_max = 0;   // the cell whose maximum is pending in cell_max
+
+  __device__ __forceinline__ void flush()
+  {
+    // the map only ever grows, so a stale read can only be too small: the atomic is skipped when it could not raise the cell
+    if (cell != 0xffffffffu && cell_max > cells[cell]) atomicMax(cells + cell, cell_max);
+    cell_max = 0;
+  }
+  __device__ __forceinline__ void voxel(T ref, uint64_t i, uint32_t x, uint32_t y, uint32_t z)
+  {
+    const T dec = convert_value<T>(values[i - b], c);
+    const double a = fabs((double)dec - (double)ref);
+    if (a > mx) { mx = a; mi = i; }   // (i only grows inside a lane: the first of equals stays; a NaN never wins)
+    int64_t q; uint32_t aq; bool nan;
+    quantise<T>(dec, ref, k, q, aq, nan);
+    n_nan += nan ? 1 : 0;
+    if (aq) {
+      ++n_over;
+      const uint32_t cl = g.cell(x, y, z);
+      if (cl != cell) { flush(); cell = cl; }
+      cell_max = std::max(cell_max, aq);
+    }
+  }
+  __device__ __forceinline__ void one(const T* p, uint64_t i)
+  {
+    uint32_t x, y, z;
+    split_index(i, bx, by, x, y, z);
+    voxel(*p, i, x, y, z);
+  }
+  __device__ __forceinline__ void piece(const T* p, uint64_t i)
+  {
+    const Piece<T> pc = *reinterpret_cast<const Piece<T>*>(p);   // one 16-byte vector load
+    uint32_t x, y, z;
+    split_index(i, bx, by, x, y, z);
+#pragma unroll
+    for (int j = 0; j < PieceOf<T>::n; ++j) {
+      voxel(pc.v[j], i + j, x, y, z);
+      if (++x == (uint32_t)bx) { x = 0; if (++y == (uint32_t)by) { y = 0; ++z; } }   // (a dense grid: a piece may run over the end of a row)
+    }
+  }
+};
+
+template <typename T>
+__global__ void __launch_bounds__(kBlock) correction_measure_kernel(const T* __restrict__ ref, BoxLayout L, uint64_t b, uint64_t e, const float* __restrict__ values,
+                                                                    Conversion c, Quantiser k, CellGrid g, uint32_t* __restrict__ cells,
+                                                                    Partial* __restrict__ partials)
+{
+  MeasureOp<T> op{values, b, c, k, L.bx, L.by, g, cells};
+  for_each_chunk_voxel<const T>(ref, L, b, e, op);
+  op.flush();
+  block_reduce(op.mx, op.mi, op.n_over, op.n_nan);
+  if (threadIdx.x == 0) merge_partial(partials, op.mx, op.mi, op.n_over, op.n_nan);
+}
+
+// ---- the cell table, read with the entry cached while a lane stays in one cell -----------------------------------------------------------
+struct TableReader {
+  const CorrectionTableEntry* __restrict__ table;
+  uint32_t cell = 0xffffffffu;
+  CorrectionTableEntry entry{~0ull, 0, 0};
+  __device__ __forceinline__ const CorrectionTableEntry& at(uint32_t cl)
+  {
+    if (cl != cell) { entry = table[cl]; cell = cl; }
+    return entry;
+  }
+};
+
+template <typename C>
+__device__ __forceinline__ void store_code(uint8_t* payload, uint64_t offset, uint32_t li, int64_t q)
+{
+  reinterpret_cast<C*>(payload + offset)[li] = (C)q;
+}
+
+// ---- pass 2: the codes of the flagged cells, the error after --------------------------------------------------------------------------------
+template <typename T>
+struct EncodeOp {
+  const float* __restrict__ values;
+  uint64_t b;
+  Conversion c;
+  Quantiser k;
+  uint64_t bx, by;
+  CellGrid g;
+  TableReader table;
+  uint8_t* __restrict__ payload;
+  double mx = -1.0;
+  uint64_t mi = ~0ull;
+
+  __device__ __forceinline__ void voxel(T ref, uint64_t i, uint32_t x, uint32_t y, uint32_t z)
+  {
+    const T dec = convert_value<T>(values[i - b], c);
+    const CorrectionTableEntry& en = table.at(g.cell(x, y, z));
+    T out = dec;
+    if (en.offset != ~0ull) {
+      const uint32_t li = g.local(x, y, z);
+      if constexpr (std::is_floating_point_v<T>) {
+        if (k.kind == kCorrectionVerbatim) {   // the code is ref's bit pattern, for every voxel of the cell
+          reinterpret_cast<typename BitsOf<T>::type*>(payload + en.offset)[li] = bits_of(ref);
+          out = ref;
+        }
+      }
+      if (k.kind != kCorrectionVerbatim) {
+        int64_t q; uint32_t aq; bool nan;
+        quantise<T>(dec, ref, k, q, aq, nan);
+        // every code byte is written exactly once: the voxel owns bytes [li * width, (li + 1) * width) of its cell
+        if (en.width == 1) store_code<int8_t>(payload, en.offset, li, q);
+        else if (en.width == 2) store_code<int16_t>(payload, en.offset, li, q);
+        else store_code<int32_t>(payload, en.offset, li, q);
+        out = corrected_value<T>(dec, q, k);
+      }
+    }
+    const double a = fabs((double)out - (double)ref);
+    if (a > mx) { mx = a; mi = i; }
+  }
+  __device__ __forceinline__ void one(const T* p, uint64_t i)
+  {
+    uint32_t x, y, z;
+    split_index(i, bx, by, x, y, z);
+    voxel(*p, i, x, y, z);
+  }
+  __device__ __forceinline__ void piece(const T* p, uint64_t i)
+  {
+    const Piece<T> pc = *reinterpret_cast<const Piece<T>*>(p);
+    uint32_t x, y, z;
+    split_index(i, bx, by, x, y, z);
+#pragma unroll
+    for (int j = 0; j < PieceOf<T>::n; ++j) {
+      voxel(pc.v[j], i + j, x, y, z);
+      if (++x == (uint32_t)bx) { x = 0; if (++y == (uint32_t)by) { y = 0; ++z; } }
+    }
+  }
+};
+
+template <typename T>
+__global__ void __launch_bounds__(kBlock) correction_encode_kernel(const T* __restrict__ ref, BoxLayout L, uint64_t b, uint64_t e, const float* __restrict__ values,
+                                                                   Conversion c, Quantiser k, CellGrid g, const CorrectionTableEntry* __restrict__ table,
+                                                                   uint8_t* __restrict__ payload, Partial* __restrict__ partials)
+{
+  EncodeOp<T> op{values, b, c, k, L.bx, L.by, g, TableReader{table}, payload};
+  for_each_chunk_voxel<const T>(ref, L, b, e, op);
+  uint64_t na = 0, nb = 0;
+  block_reduce(op.mx, op.mi, na, nb);
+  if (threadIdx.x == 0) merge_partial(partials, op.mx, op.mi, 0, 0);
+}
+
+// ---- the apply: decode, look up, correct, store ------------------------------------------------------------------------------------------------
+template <typename T>
+struct ApplyOp {
+  const float* __restrict__ values;
+  uint64_t b;
+  Conversion c;
+  Quantiser k;
+  uint64_t bx, by;
+  CellGrid g;
+  TableReader table;
+  const uint8_t* __restrict__ payload;
+
+  __device__ __forceinline__ T voxel(uint64_t i, uint32_t x, uint32_t y, uint32_t z)
+  {
+    const T dec = convert_value<T>(values[i - b], c);
+    const CorrectionTableEntry& en = table.at(g.cell(x, y, z));
+    if (en.offset == ~0ull) return dec;
+    const uint32_t li = g.local(x, y, z);
+    const uint8_t* codes = payload + en.offset;
+    if constexpr (std::is_floating_point_v<T>) {
+      if (k.kind == kCorrectionVerbatim) {
+        const typename BitsOf<T>::type bits = reinterpret_cast<const typename BitsOf<T>::type*>(codes)[li];
+        T v;
+        __builtin_memcpy(&v, &bits, sizeof(T));
+        return v;
+      }
+    }
+    const int64_t q = en.width == 1 ? (int64_t)reinterpret_cast<const int8_t*>(codes)[li]
+                                    : (en.width == 2 ? (int64_t)reinterpret_cast<const int16_t*>(codes)[li] : (int64_t)reinterpret_cast<const int32_t*>(codes)[li]);
+    return corrected_value<T>(dec, q, k);
+  }
+  __device__ __forceinline__ void one(T* p, uint64_t i)
+  {
+    uint32_t x, y, z;
+    split_index(i, bx, by, x, y, z);
+    *p = voxel(i, x, y, z);
+  }
+  __device__ __forceinline__ void piece(T* p, uint64_t i)
+  {
+    Piece<T> pc;
+    uint32_t x, y, z;
+    split_index(i, bx, by, x, y, z);
+#pragma unroll
+    for (int j = 0; j < PieceOf<T>::n; ++j) {
+      pc.v[j] = voxel(i + j, x, y, z);
+      if (++x == (uint32_t)bx) { x = 0; if (++y == (uint32_t)by) { y = 0; ++z; } }
+    }
+    *reinterpret_cast<Piece<T>*>(p) = pc;   // one 16-byte vector store
+  }
+};
+
+template <typename T>
+__global__ void __launch_bounds__(kBlock) correction_apply_kernel(T* __restrict__ dst, BoxLayout L, uint64_t b, uint64_t e, const float* __restrict__ values,
+                                                                  Conversion c, Quantiser k, CellGrid g, const CorrectionTableEntry* __restrict__ table,
+                                                                  const uint8_t* __restrict__ payload)
+{
+  ApplyOp<T> op{values, b, c, k, L.bx, L.by, g, TableReader{table}, payload};
+  for_each_chunk_voxel<T>(dst, L, b, e, op);
+}
+
+// ---- host side: decode.hip's dispatch, validation and chunking ------------------------------------------------------------------------------
+template <typename F>
+void dispatch_type(int type, F&& f)
+{
+  switch (type) {
+  case 0: f((uint8_t*)nullptr); break;
+  case 1: f((int8_t*)nullptr); break;
+  case 2: f((uint16_t*)nullptr); break;
+  case 3: f((int16_t*)nullptr); break;
+  case 4: f((uint32_t*)nullptr); break;
+  case 5: f((int32_t*)nullptr); break;
+  case 8: f((float*)nullptr); break;
+  case 12: f((double*)nullptr); break;
+  default: throw std::runtime_error("unknown value type " + std::to_string(type));
+  }
+}
+
+// where the runtime knows the allocation a pointer lies in, what the call will touch must fit into it
+void require_room(const void* p, size_t bytes, const char* what)
+{
+  void* base = nullptr; size_t size = 0;
+  if (hipMemGetAddressRange((hipDeviceptr_t*)&base, &size, (hipDeviceptr_t)p) != hipSuccess || !base || !size) {
+    (void)hipGetLastError();   // not a pointer the runtime can place: taken as given
+    return;
+  }
+  const size_t room = (size_t)((const char*)base + size - (const char*)p);
+  if (bytes > room)
+    throw std::runtime_error(std::string(what) + " spans " + std::to_string(bytes) + " bytes from its device pointer, the allocation has " + std::to_string(room) + " left");
+}
+
+// everything decode.hip refuses a whole-grid array for, with its messages; returns the layout of the grid in the caller's array
+BoxLayout validate_grid_array(const void* data, int type, const int64_t* strides, vec3i grid, float range_lo, float range_hi)
+{
+  if (!data) throw std::runtime_error("null device data");
+  const size_t ts = device_value_type_size(type);   // refuses the 64-bit integer and the vector types like the ingest
+  if (grid.x <= 0 || grid.y <= 0 || grid.z <= 0)
+    throw std::runtime_error("grid dimensions must be positive: " + std::to_string(grid.x) + " x " + std::to_string(grid.y) + " x " + std::to_string(grid.z));
+  const bool integer = type != 8 && type != 12;
+  if (!(range_lo < range_hi) && !(range_lo > range_hi)) throw std::runtime_error("range_lo == range_hi (or a NaN): an empty value range");
+  if (integer && range_lo > range_hi) throw std::runtime_error("an integer value type needs a value range (range_lo < range_hi)");
+
+  BoxLayout L{};
+  L.bx = (uint64_t)grid.x; L.by = (uint64_t)grid.y; L.bz = (uint64_t)grid.z;
+  L.sx = strides ? strides[0] : 1;
+  L.sy = strides ? strides[1] : (int64_t)L.bx;
+  L.sz = strides ? strides[2] : (int64_t)(L.bx * L.by);
+  const int64_t s[3] = {L.sx, L.sy, L.sz};
+  const uint64_t n[3] = {L.bx, L.by, L.bz};
+  for (int a = 0; a < 3; ++a)
+    if (s[a] <= 0) throw std::runtime_error("strides must be positive: stride " + std::to_string(a) + " is " + std::to_string(s[a]));
+  // no two voxels at one address: the axes longer than one voxel, ordered by stride, must nest
+  int order[3] = {0, 1, 2};
+  std::sort(order, order + 3, [&](int a, int b) { return s[a] < s[b]; });
+  unsigned __int128 extent = 1, last = 0;   // elements the axes so far span; offset of the last voxel
+  for (int k = 0; k < 3; ++k) {
+    const int a = order[k];
+    if (n[a] == 1) continue;
+    if ((unsigned __int128)s[a] < extent)
+      throw std::runtime_error("the strides (" + std::to_string(L.sx) + ", " + std::to_string(L.sy) + ", " + std::to_string(L.sz) +
+                               ") overlap: two voxels of the box would share an address");
+    extent = (unsigned __int128)s[a] * (n[a] - 1) + extent;
+  }
+  for (int a = 0; a < 3; ++a) last += (unsigned __int128)s[a] * (n[a] - 1);
+  if ((last + 1) * ts > (unsigned __int128)INT64_MAX) throw std::runtime_error("the strides span more than 2^63 bytes");
+  if ((uintptr_t)data % ts != 0) throw std::runtime_error("device data is not aligned to its value type (" + std::to_string(ts) + " bytes)");
+  require_room(data, (size_t)((last + 1) * ts), "the box");
+
+  L.gather = L.sx != 1;
+  if (!L.gather) {
+    // contiguous runs: the whole grid, whole slices, or x-rows
+    if (L.sy == (int64_t)L.bx && L.sz == (int64_t)(L.bx * L.by)) { L.run_len = L.bx * L.by * L.bz; L.runs_y = 1; L.sy = 0; L.sz = 0; }
+    else if (L.sy == (int64_t)L.bx) { L.run_len = L.bx * L.by; L.runs_y = 1; L.sy = 0; }
+    else { L.run_len = L.bx; L.runs_y = L.by; }
+  }
+  return L;
+}
+
+// launch width for the chunk [b, e): its pieces of work (for_each_chunk_voxel), the rest by block stride
+uint32_t chunk_grid(const BoxLayout& L, int type, uint64_t b, uint64_t e)
+{
+  uint64_t work = e - b;
+  if (!L.gather) {
+    const uint64_t per = 16 / device_value_type_size(type);
+    work = ((e - 1) / L.run_len - b / L.run_len + 1) * (1 + (std::min(L.run_len, e - b) + per - 1) / per);
+  }
+  const uint64_t blocks = (work + kBlock - 1) / kBlock;
+  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)Runtime::get().n_cus * 8));
+}
+
+uint64_t chunk_samples()
+{
+  uint64_t c = kDefaultChunk;
+  if (const char* e = std::getenv("VNR_AMD_DECODE_CHUNK")) {
+    char* end = nullptr;
+    const unsigned long long v = std::strtoull(e, &end, 10);
+    if (end == e || *end != '\0' || v == 0) throw std::runtime_error(std::string("VNR_AMD_DECODE_CHUNK must be a positive sample count, got '") + e + "'");
+    c = std::min<uint64_t>(v, kMaxChunk);
+  }
+  return c;
+}
+
+struct EventGuard {
+  hipEvent_t e = nullptr;
+  ~EventGuard() { if (e) (void)hipEventDestroy(e); }
+};
+
+// the library's stream waits for what the caller's stream holds at this point; the caller's stream is not touched otherwise
+void wait_for(hipStream_t theirs, hipStream_t ours, EventGuard& ev)
+{
+  if (!theirs) return;
+  VNR_HIP_CHECK(hipEventCreateWithFlags(&ev.e, hipEventDisableTiming));
+  VNR_HIP_CHECK(hipEventRecord(ev.e, theirs));
+  VNR_HIP_CHECK(hipStreamWaitEvent(ours, ev.e, 0));
+}
+
+Quantiser make_quantiser(uint32_t kind, double eps)
+{
+  Quantiser k{kind, 0, 1, 1, 1.0};
+  if (kind == kCorrectionInteger) {
+    k.E = (int64_t)std::floor(std::min(eps, kCorrectionMaxIntegerEps));
+    k.s = 2 * k.E + 1;
+    k.qmax = (1ll << 34) / k.s + 1;
+  } else if (kind == kCorrectionFloat) {
+    k.sd = 2.0 * eps;
+  }
+  return k;
+}
+
+CellGrid make_cell_grid(vec3i d)
+{
+  return CellGrid{(uint32_t)d.x, (uint32_t)d.y, (uint32_t)d.z, (uint32_t)((d.x + 15) / 16), (uint32_t)((d.y + 15) / 16)};
+}
+
+// per-cell {offset, width} of all n_cells cells from the flagged ones, in payload order
+std::vector<CorrectionTableEntry> make_table(const CorrectionData& d, uint64_t n_cells)
+{
+  std::vector<CorrectionTableEntry> t(n_cells, CorrectionTableEntry{~0ull, 0, 0});
+  uint64_t offset = 0;
+  for (const CorrectionCellEntry& e : d.cells) {
+    t[e.cell] = CorrectionTableEntry{offset, e.width, 0};
+    offset += correction_padded_bytes(correction_cell_voxels(d.h.dims, e.cell), e.width);
+  }
+  return t;
+}
+
+void index_to_voxel(uint64_t i, const BoxLayout& L, int out[3])
+{
+  const uint64_t yz = i / L.bx;
+  out[0] = (int)(i - yz * L.bx); out[1] = (int)(yz % L.by); out[2] = (int)(yz / L.by);
+}
+
+}  // namespace
+
+uint64_t NeuralVolume::params_hash()
+{
+  std::vector<uint16_t> p(net_.n_params());
+  net_.get_params_f16(p.data(), p.size(), stream);
+  return fnv1a64(p.data(), p.size() * sizeof(uint16_t));
+}
+
+std::shared_ptr<Correction> NeuralVolume::build_correction(const DeviceSource& ref, float range_lo, float range_hi, double eps)
+{
+  if (!net_.valid()) throw std::runtime_error("neural volume has no valid network");
+  if (!(eps >= 0.0) || !std::isfinite(eps)) throw std::runtime_error("eps must be a finite tolerance >= 0 in data units, got " + std::to_string(eps));
+  const vec3i grid = desc.dims;
+  const BoxLayout L = validate_grid_array(ref.data, ref.type, ref.strides, grid, range_lo, range_hi);
+  const uint64_t total = L.bx * L.by * L.bz, chunk = std::min(chunk_samples(), total);
+  const vec3f rdims = {1.0f / (float)grid.x, 1.0f / (float)grid.y, 1.0f / (float)grid.z};
+  const vec3i lower{0, 0, 0};
+  const Conversion c{range_lo, range_hi - range_lo, range_lo < range_hi};
+  const bool is_float = correction_type_is_float(ref.type);
+  const uint32_t kind = !is_float ? kCorrectionInteger : (eps > 0.0 ? kCorrectionFloat : kCorrectionVerbatim);
+  const Quantiser k = make_quantiser(kind, eps);
+  const CellGrid g = make_cell_grid(grid);
+  const int dims[3] = {grid.x, grid.y, grid.z};
+  const uint64_t n_cells = correction_n_cells(dims);
+
+  auto corr = std::make_shared<Correction>();
+  CorrectionHeader& h = corr->data.h;
+  h.value_type = ref.type;
+  for (int a = 0; a < 3; ++a) h.dims[a] = dims[a];
+  h.eps = eps; h.range_lo = range_lo; h.range_hi = range_hi; h.kind = kind;
+  h.step = correction_step(kind, eps);
+  h.n_params = net_.n_params();
+  h.params_hash = params_hash();
+
+  const uint32_t max_blocks = (uint32_t)Runtime::get().n_cus * 8;
+  dd_coords_.ensure(3 * chunk);
+  dd_values_.ensure(chunk);
+  static_assert(sizeof(Partial) == 4 * sizeof(double), "Partial is laid over dd_partials_");
+  dd_partials_.ensure((size_t)(max_blocks + 1) * (sizeof(Partial) / sizeof(double)));
+  Partial* partials = (Partial*)dd_partials_.ptr;
+  Partial* d_result = partials + max_blocks;
+  DeviceBuffer<uint32_t> cell_max(MemTag::Network);
+  cell_max.resize(n_cells);
+  EventGuard ev;
+  wait_for(ref.producer, stream, ev);   // the reference is complete once the caller's stream reaches this point
+
+  // pass 1
+  correction_init_kernel<<<div_round_up(max_blocks, kBlock), kBlock, 0, stream>>>(partials, max_blocks);
+  VNR_HIP_CHECK(hipGetLastError());
+  cell_max.zero(stream);
+  for (uint64_t b = 0; b < total; b += chunk) {
+    const uint64_t e = std::min(total, b + chunk);
+    decode_chunk(b, (uint32_t)(e - b), L.bx, L.by, lower, rdims, dd_values_.ptr);
+    const uint32_t blocks = chunk_grid(L, ref.type, b, e);
+    dispatch_type(ref.type, [&](auto* tag) {
+      using T = std::remove_pointer_t<decltype(tag)>;
+      correction_measure_kernel<T><<<blocks, kBlock, 0, stream>>>((const T*)ref.data, L, b, e, dd_values_.ptr, c, k, g, cell_max.ptr, partials);
+    });
+    VNR_HIP_CHECK(hipGetLastError());
+  }
+  correction_final_kernel<<<1, kBlock, 0, stream>>>(partials, max_blocks, d_result);
+  VNR_HIP_CHECK(hipGetLastError());
+  Partial before;
+  std::vector<uint32_t> cells(n_cells);
+  VNR_HIP_CHECK(hipMemcpyAsync(&before, d_result, sizeof(before), hipMemcpyDeviceToHost, stream));
+  cell_max.download(cells.data(), n_cells, stream);   // (synchronises)
+
+  // the table
+  const uint32_t ts = (uint32_t)device_value_type_size(ref.type);
+  uint64_t payload_bytes = 0;
+  for (uint64_t cl = 0; cl < n_cells; ++cl) {
+    const uint32_t m = cells[cl];
+    if (m == 0) continue;
+    if (m > 0x7fffffffu) throw std::runtime_error("the tolerance needs codes wider than 32 bits: eps " + std::to_string(eps) + " against a maximum error of " + std::to_string(before.max_abs));
+    const uint32_t width = kind == kCorrectionVerbatim ? ts : (m <= 127 ? 1u : (m <= 32767 ? 2u : 4u));
+    corr->data.cells.push_back(CorrectionCellEntry{(uint32_t)cl, width});
+    payload_bytes += correction_padded_bytes(correction_cell_voxels(dims, (uint32_t)cl), width);
+  }
+  corr->n_voxels_flagged = before.n_a;
+  corr->n_nan = before.n_b;
+  corr->max_abs_before = before.max_abs < 0.0 ? std::numeric_limits<double>::quiet_NaN() : before.max_abs;
+  Partial after = before;   // without a flagged cell every voxel stays as decoded
+  if (!corr->data.cells.empty()) {
+    const std::vector<CorrectionTableEntry> table = make_table(corr->data, n_cells);
+    corr->d_table.upload(table.data(), table.size(), stream);
+    corr->d_payload.resize(payload_bytes);
+    corr->d_payload.zero(stream);   // (the padding, and what no voxel owns, stays zero)
+    // pass 2: the network a second time
+    correction_init_kernel<<<div_round_up(max_blocks, kBlock), kBlock, 0, stream>>>(partials, max_blocks);
+    VNR_HIP_CHECK(hipGetLastError());
+    for (uint64_t b = 0; b < total; b += chunk) {
+      const uint64_t e = std::min(total, b + chunk);
+      decode_chunk(b, (uint32_t)(e - b), L.bx, L.by, lower, rdims, dd_values_.ptr);
+      const uint32_t blocks = chunk_grid(L, ref.type, b, e);
+      dispatch_type(ref.type, [&](auto* tag) {
+        using T = std::remove_pointer_t<decltype(tag)>;
+        correction_encode_kernel<T><<<blocks, kBlock, 0, stream>>>((const T*)ref.data, L, b, e, dd_values_.ptr, c, k, g, corr->d_table.ptr, corr->d_payload.ptr,
+                                                                   partials);
+      });
+      VNR_HIP_CHECK(hipGetLastError());
+    }
+    correction_final_kernel<<<1, kBlock, 0, stream>>>(partials, max_blocks, d_result);
+    VNR_HIP_CHECK(hipGetLastError());
+    VNR_HIP_CHECK(hipMemcpyAsync(&after, d_result, sizeof(after), hipMemcpyDeviceToHost, stream));
+    corr->data.payload.resize(payload_bytes);
+    corr->d_payload.download(corr->data.payload.data(), payload_bytes, stream);   // (synchronises: `table` and `after` are done with)
+  }
+  corr->uploaded = true;
+  if (after.max_abs < 0.0) {   // every voxel's error is a NaN
+    h.max_abs_after = std::numeric_limits<double>::quiet_NaN();
+  } else {
+    h.max_abs_after = after.max_abs;
+    index_to_voxel(after.worst, L, corr->worst_after);
+  }
+  return corr;
+}
+
+void NeuralVolume::decode_to_device_corrected(Correction& corr, const DeviceTarget& out, bool verify_params)
+{
+  if (!net_.valid()) throw std::runtime_error("neural volume has no valid network");
+  const CorrectionHeader& h = corr.data.h;
+  const vec3i grid = desc.dims;
+  if (h.dims[0] != grid.x || h.dims[1] != grid.y || h.dims[2] != grid.z)
+    throw std::runtime_error("the correction's dims (" + std::to_string(h.dims[0]) + " x " + std::to_string(h.dims[1]) + " x " + std::to_string(h.dims[2]) +
+                             ") differ from the volume's (" + std::to_string(grid.x) + " x " + std::to_string(grid.y) + " x " + std::to_string(grid.z) + ")");
+  const BoxLayout L = validate_grid_array(out.data, h.value_type, out.strides, grid, h.range_lo, h.range_hi);
+  const uint64_t chunk_limit = chunk_samples();
+  if (verify_params) {
+    if (h.n_params != (uint64_t)net_.n_params())
+      throw std::runtime_error("the correction was built on " + std::to_string(h.n_params) + " parameters, the volume has " + std::to_string(net_.n_params()));
+    if (h.params_hash != params_hash()) throw std::runtime_error("the volume's parameters are not the ones the correction was built on (their hash differs)");
+  }
+  if (corr.data.cells.empty()) {   // nothing to apply: the plain decode
+    decode_to_device(DeviceTarget{out.data, h.value_type, out.strides, out.consumer}, nullptr, nullptr, nullptr, h.range_lo, h.range_hi);
+    return;
+  }
+  const int dims[3] = {grid.x, grid.y, grid.z};
+  if (!corr.uploaded) {
+    const std::vector<CorrectionTableEntry> table = make_table(corr.data, correction_n_cells(dims));
+    corr.d_table.upload(table.data(), table.size(), stream);
+    corr.d_payload.upload(corr.data.payload.data(), corr.data.payload.size(), stream);
+    VNR_HIP_CHECK(hipStreamSynchronize(stream));   // `table` goes out of scope
+    corr.uploaded = true;
+  }
+  const uint64_t total = L.bx * L.by * L.bz, chunk = std::min(chunk_limit, total);
+  const vec3f rdims = {1.0f / (float)grid.x, 1.0f / (float)grid.y, 1.0f / (float)grid.z};
+  const vec3i lower{0, 0, 0};
+  const Conversion c{h.range_lo, h.range_hi - h.range_lo, h.range_lo < h.range_hi};
+  const Quantiser k = make_quantiser(h.kind, h.eps);
+  const CellGrid g = make_cell_grid(grid);
+  dd_coords_.ensure(3 * chunk);
+  dd_values_.ensure(chunk);
+  EventGuard ev;
+  wait_for(out.consumer, stream, ev);   // what the destination held may still be being read
+  for (uint64_t b = 0; b < total; b += chunk) {
+    const uint64_t e = std::min(total, b + chunk);
+    decode_chunk(b, (uint32_t)(e - b), L.bx, L.by, lower, rdims, dd_values_.ptr);
+    const uint32_t blocks = chunk_grid(L, h.value_type, b, e);
+    dispatch_type(h.value_type, [&](auto* tag) {
+      using T = std::remove_pointer_t<decltype(tag)>;
+      correction_apply_kernel<T><<<blocks, kBlock, 0, stream>>>((T*)out.data, L, b, e, dd_values_.ptr, c, k, g, corr.d_table.ptr, corr.d_payload.ptr);
+    });
+    VNR_HIP_CHECK(hipGetLastError());
+  }
+  VNR_HIP_CHECK(hipStreamSynchronize(stream));   // on return the grid is there
+}
+
+}  // namespace vnr

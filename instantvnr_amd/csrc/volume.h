@@ -9,6 +9,7 @@
 #include <memory>
 
 #include "common.h"
+#include "correction_format.h"
 #include "json.h"
 #include "network.h"
 #include "ooc_sampler.h"
@@ -107,6 +108,19 @@ struct DecodeError {
   double max_abs;
   int worst[3];
   double sum_abs, sum_sq, psnr_db;
+};
+
+// An error-bound correction (correction.hip; vnrAmdCorrection of include/vnr_amd.h): the serialisable part on the host, the report of the
+// build that made it, and the device copies the apply reads (a correction loaded from bytes uploads them at its first use).
+struct CorrectionTableEntry { uint64_t offset; uint32_t width, pad; };   // per macrocell: byte offset of its codes in the payload, or ~0
+struct Correction {
+  CorrectionData data;
+  uint64_t n_voxels_flagged = 0, n_nan = 0;
+  double max_abs_before = 0.0;
+  int worst_after[3] = {-1, -1, -1};
+  DeviceBuffer<uint8_t> d_payload{MemTag::Network};
+  DeviceBuffer<CorrectionTableEntry> d_table{MemTag::Network};
+  bool uploaded = false;
 };
 
 struct VolumeDesc {  // MultiVolume, instantvnr_types.h:40-56 (single timestep)
@@ -256,6 +270,14 @@ public:
   void decode_to_device(const DeviceTarget& out, const int box_lo[3], const int box_size[3], const int grid_dims[3], float range_lo, float range_hi);
   void error_against_device(const DeviceSource& ref, const int box_lo[3], const int box_size[3], float range_lo, float range_hi, DecodeError* result,
                             float* d_block_max);
+  // Error-bounded round trip (correction.hip; no reference counterpart; the arithmetic is spelled out in include/vnr_amd.h).
+  // build_correction: quantised residuals of exactly the macrocells where some voxel of the whole-grid decode (value type of `ref`,
+  // this range) misses `eps` against `ref`; two chunked passes, the network evaluated in each, no full-size intermediate.
+  // decode_to_device_corrected: decode_to_device of the whole grid with the correction applied (type and range are the correction's;
+  // out.type is ignored).  verify_params: refuse unless the parameters hash to what the correction was built on.
+  std::shared_ptr<Correction> build_correction(const DeviceSource& ref, float range_lo, float range_hi, double eps);
+  void decode_to_device_corrected(Correction& corr, const DeviceTarget& out, bool verify_params);
+  uint64_t params_hash();   // FNV-1a 64 of the fp16 parameter blob
   // network.cu:328-365 / :367-405: raw fp32, z-slice by z-slice, every slice padded to a multiple of 256 values
   void save_inference_volume(const std::string& filename);
   void save_reference_volume(const std::string& filename);

@@ -19,6 +19,11 @@ ingest time are printed.
                          (vnrAmdNeuralVolumeErrorAgainstDevice), and a decode into a device array of the source's type and ghost
                          layers (vnrAmdNeuralVolumeDecodeToDevice); both timed, beside vnrAmdNeuralVolumeInference on the same
                          number of ready-made coordinates
+  --error-bound EPS      after each step's training: a correction for the tolerance EPS (data units, >= 0) against the step's own
+                         device array (vnrAmdNeuralVolumeBuildCorrection) and a decode with it applied into a device array of the
+                         source's type and ghost layers (vnrAmdNeuralVolumeDecodeToDeviceCorrected).  Per step: the raw bytes, the
+                         params.json bytes plus the correction's bytes and the ratio, the flagged cells, the largest error before
+                         and after; both calls timed, beside ErrorAgainstDevice and DecodeToDevice on the same arrays
   --guided               error-guided batches instead of the series (vnrAmdNeuralVolumeGuideSamplingByError): ONE static field, the
                          synthetic blob field with plateaus at both ends, trained --steps-per-frame steps in all, twice with the same
                          seeds: once with the error map re-installed as sampling weights every --refresh-every steps, once with
@@ -37,7 +42,11 @@ The --round-trip times are host clocks as well, each around one call that return
 "error" are the whole calls (coordinate kernel + evaluation + store or reduce kernel per chunk of VNR_AMD_DECODE_CHUNK samples),
 "inference" is one vnrAmdNeuralVolumeInference call + synchronise over the same voxel centres as ready-made coordinates, so
 "decode - inference" is a difference of wall times.  Each is run once to warm up, then --repeat times.  The kernels are decode_coords_kernel, decode_store_kernel,
-decode_error_kernel and decode_error_final_kernel."""
+decode_error_kernel and decode_error_final_kernel.
+
+The --error-bound times are host clocks around whole calls in the same way: "build" evaluates the network twice and brings the codes
+to the host, "apply" evaluates it once.  The kernels are correction_measure_kernel, correction_encode_kernel and
+correction_apply_kernel."""
 import argparse
 import json
 import os
@@ -112,6 +121,37 @@ def round_trip(neural, ptr, dtype, strides, dims, ghost, value_range, repeat, co
     return row
 
 
+def error_bound(neural, ptr, dtype, strides, dims, ghost, value_range, eps, repeat):
+    """-> the --error-bound columns of one step.  `ptr` is the step's own device array (the reference of the correction)."""
+    def build():
+        c = api.vnrNeuralVolumeBuildCorrection(neural, ptr, dtype, eps, strides, value_range)
+        held.append(c)
+        while len(held) > 1:
+            held.pop(0).release()
+        return c
+    held = []
+    corr, best, median = timed(build, repeat, 1)
+    info = corr.info()
+    raw = dims[0] * dims[1] * dims[2] * dtype.itemsize
+    n_params = len(api.vnrNeuralVolumeSerializeParams(neural))
+    row = {"eps": eps, "raw_bytes": raw, "params_bytes": n_params, "correction_bytes": info["serialized_bytes"],
+           "compressed_bytes": n_params + info["serialized_bytes"], "ratio": round(raw / (n_params + info["serialized_bytes"]), 3),
+           "flagged_cells": info["n_flagged"], "cells": info["n_cells"], "voxels_over": info["n_voxels_flagged"],
+           "max_abs_before": info["max_abs_before"], "max_abs_after": info["max_abs_after"], "build_ms": round(best, 4), "build_median_ms": round(median, 4)}
+    padded = tuple(d + 2 * ghost for d in dims)
+    out = api.DeviceArray((padded[2], padded[1], padded[0]), dtype)
+    first = (ghost + ghost * padded[0] + ghost * padded[0] * padded[1]) * dtype.itemsize
+    _, best, median = timed(lambda: api.vnrNeuralVolumeDecodeToDeviceCorrected(neural, corr, out.ptr + first, strides), repeat, 1)
+    row.update(apply_ms=round(best, 4), apply_median_ms=round(median, 4))
+    _, best, median = timed(lambda: api.vnrNeuralVolumeDecodeToDevice(neural, out.ptr + first, dtype, strides, None, None, value_range), repeat, 1)
+    row.update(plain_decode_ms=round(best, 4), plain_decode_median_ms=round(median, 4))
+    _, best, median = timed(lambda: api.vnrNeuralVolumeErrorAgainstDevice(neural, ptr, dtype, strides, None, value_range), repeat, 1)
+    row.update(error_report_ms=round(best, 4), error_report_median_ms=round(median, 4))
+    out.free()
+    corr.release()
+    return row
+
+
 def guided(a):
     """the --guided run: the same field, model and seeds trained with error-guided and with uniform batches, side by side"""
     dims = (a.size,) * 3
@@ -166,6 +206,7 @@ def main(argv=None):
     p.add_argument("--repeat", type=int, default=5)
     p.add_argument("--compare-host", action="store_true")
     p.add_argument("--round-trip", action="store_true")
+    p.add_argument("--error-bound", type=float, default=None, metavar="EPS")
     p.add_argument("--guided", action="store_true")
     p.add_argument("--uniform-fraction", type=float, default=0.25)
     p.add_argument("--refresh-every", type=int, default=100)
@@ -175,6 +216,8 @@ def main(argv=None):
         p.error("--guided needs --steps-per-frame > 0, --refresh-every > 0 and --uniform-fraction in [0, 1]")
     if a.round_trip and not a.steps_per_frame:
         p.error("--round-trip needs a trained network: --steps-per-frame > 0")
+    if a.error_bound is not None and (not a.steps_per_frame or not a.error_bound >= 0.0 or a.error_bound == float("inf")):
+        p.error("--error-bound needs a trained network (--steps-per-frame > 0) and a finite EPS >= 0")
 
     api._lib.require_device()
     api.check(api.lib().vnrAmdInit(-1))
@@ -224,6 +267,8 @@ def main(argv=None):
             row["psnr"] = round(api.vnrNeuralVolumeGetPSNR(neural), 3)
             if a.round_trip:     # in data units: the range that was applied inverts the ingest
                 row.update(round_trip(neural, ptr, dtype, strides, dims, a.ghost, used, a.repeat, coords))
+            if a.error_bound is not None:
+                row.update(error_bound(neural, ptr, dtype, strides, dims, a.ghost, used, a.error_bound, a.repeat))
         d.free()
         for k in ("create_ms", "host_create_ms", "host_create_median_ms"):
             if k in row:

@@ -344,6 +344,31 @@ vnrAmdCorrection vnrAmdCreateCorrectionFromBytes(const void* bytes, size_t size)
 int  vnrAmdNeuralVolumeDecodeToDeviceCorrected(vnrAmdVolume neural, vnrAmdCorrection, void* d_out, const int64_t strides[3],
                                                void* stream, int verify_params);
 void vnrAmdReleaseCorrection(vnrAmdCorrection);
+/* AMD extension: packed corrections.  A second serialised form of the same correction, with a bit width per group of 64 codes and
+ * the codes stored as bit planes; "VNRCORR1" above and everything that reads or writes it is unchanged, and either form gives the
+ * other byte for byte.  Little-endian: the 104-byte header above with magic "VNRCORP1", version 1 and payload_bytes the size of the
+ * packed payload (every other field as above, with its rules); the same n_flagged entries {uint32 cell, uint32 width}, width being
+ * the code width of the cell in the fixed-width form; then the packed payload.
+ * The codes of a flagged cell are its codes above in their order, lx + cx (ly + cy lz), cut into groups of 64 consecutive codes;
+ * the last group of a cell is filled up with codes of value 0: ceil(voxels / 64) groups a cell, at most 64.  A code becomes an
+ * unsigned z of up to 64 bits: kinds 0 and 1 z = (q << 1) ^ (q >> 63) of the sign-extended code q, kind 2 the stored bit pattern,
+ * zero-extended.  nbits of a group is the bit length of its largest z, 0 to 64.  The packed payload is
+ *   1. the group table: one byte nbits per group, all groups of all flagged cells in cell order, zero bytes up to a multiple of 8;
+ *   2. the planes: group after group in that order, nbits words of uint64; bit l of word b (b = 0 the least significant plane) is
+ *      bit b of the z of the group's code l.
+ * payload_bytes = pad8(n_groups) + 8 * the sum of nbits.  A group of zeros costs its table byte.
+ *
+ * SerializePacked packs on the device, from the resident fixed-width payload (uploaded first if the correction came from bytes), on
+ * the library's stream, and has synchronised when it returns; one wavefront takes one group, a plane is one ballot.  The result is
+ * cached (a correction never changes); a correction read from packed bytes returns those bytes without touching the device.
+ * CreateCorrectionFromPackedBytes is host code like CreateCorrectionFromBytes: the packed payload is uploaded as it is and unpacked
+ * on the device by the first apply, and on the host by the first Serialize or GetInfo.  It refuses, with "malformed packed
+ * correction bytes: <rule>", everything CreateCorrectionFromBytes refuses in header and entries, and: an nbits above 8 * width, a
+ * group whose top plane is zero while nbits > 0 (the form is canonical), a set bit in a lane beyond the cell's voxels, nonzero table
+ * padding, a size that differs from header + entries + payload_bytes, payload_bytes that differ from what the table gives.
+ * Errors: a null handle, null arguments, malformed bytes; SerializePacked of a correction not read from packed bytes needs a device. */
+int  vnrAmdCorrectionSerializePacked(vnrAmdCorrection, void** bytes, size_t* size);    /* vnrAmdFreeHost */
+vnrAmdCorrection vnrAmdCreateCorrectionFromPackedBytes(const void* bytes, size_t size); /* host only; unpacked at first use */
 /* hash-grid encode only (tcnn_impl_decoder.cu:177-230, column = level*F + f): fp16 [n][padded_width] */
 int    vnrAmdNeuralVolumeEncode(vnrAmdVolume, size_t n, const float* d_coords, uint16_t* d_features, void* stream);
 /* AMD extension: state of the brick image, the de-hashed inference copy of the hashed levels (csrc/network.h).  It is built

@@ -255,6 +255,8 @@ def lib():
     sig("vnrAmdCorrectionGetInfo", I, P, C.POINTER(CorrectionInfo))
     sig("vnrAmdCorrectionSerialize", I, P, C.POINTER(P), C.POINTER(SZ))
     sig("vnrAmdCreateCorrectionFromBytes", P, P, SZ)
+    sig("vnrAmdCorrectionSerializePacked", I, P, C.POINTER(P), C.POINTER(SZ))
+    sig("vnrAmdCreateCorrectionFromPackedBytes", P, P, SZ)
     sig("vnrAmdNeuralVolumeDecodeToDeviceCorrected", I, P, P, P, I64P, P, I)
     sig("vnrAmdReleaseCorrection", None, P)
     _lib = L

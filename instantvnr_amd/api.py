@@ -511,7 +511,7 @@ def vnrNeuralVolumeErrorAgainstDevice(v, d_ptr, dtype, strides=None, box=None, v
 
 class Correction(_Handle):
     """an error-bound correction (include/vnr_amd.h, "error-bounded round trip"): built by vnrNeuralVolumeBuildCorrection or loaded
-    with Correction.from_bytes; to_bytes() beside params.json is the compressed field"""
+    with Correction.from_bytes / from_packed_bytes; to_bytes() or the smaller to_packed_bytes() beside params.json is the compressed field"""
     _release = "vnrAmdReleaseCorrection"
 
     def info(self):
@@ -535,6 +535,22 @@ class Correction(_Handle):
         """host only: the bytes are validated here, the device copy is made by the first apply"""
         b = bytes(b)
         return cls(lib().vnrAmdCreateCorrectionFromBytes(b, len(b)))
+
+    def to_packed_bytes(self):
+        """the packed form (include/vnr_amd.h, "packed corrections"): packed on the device, once; the bytes it was read from if it
+        came from_packed_bytes"""
+        out = C.c_void_p()
+        n = C.c_size_t()
+        check(lib().vnrAmdCorrectionSerializePacked(self.h, C.byref(out), C.byref(n)))
+        b = C.string_at(out, n.value)
+        lib().vnrAmdFreeHost(out)
+        return b
+
+    @classmethod
+    def from_packed_bytes(cls, b):
+        """host only: the bytes are validated here, uploaded as they are and unpacked on the device by the first apply"""
+        b = bytes(b)
+        return cls(lib().vnrAmdCreateCorrectionFromPackedBytes(b, len(b)))
 
 
 def vnrNeuralVolumeBuildCorrection(v, d_ref, dtype, eps, strides=None, value_range=None, stream=None):

@@ -605,8 +605,9 @@ vnrAmdCorrection vnrAmdNeuralVolumeBuildCorrection(vnrAmdVolume v, const void* d
 int vnrAmdCorrectionGetInfo(vnrAmdCorrection c, vnrAmdCorrectionInfo* out)
 {
   return guarded([&]() {
-    const Correction* k = as_correction(c);
+    Correction* k = as_correction(c);
     if (!out) throw std::runtime_error("null result");
+    k->host_payload();   // (a correction read from packed bytes: its fixed-width sizes)
     const CorrectionHeader& h = k->data.h;
     *out = vnrAmdCorrectionInfo{};
     for (int a = 0; a < 3; ++a) { out->dims[a] = h.dims[a]; out->worst_after[a] = k->worst_after[a]; }
@@ -619,8 +620,9 @@ int vnrAmdCorrectionGetInfo(vnrAmdCorrection c, vnrAmdCorrectionInfo* out)
 int vnrAmdCorrectionSerialize(vnrAmdCorrection c, void** bytes, size_t* size)
 {
   return guarded([&]() {
-    const Correction* k = as_correction(c);
+    Correction* k = as_correction(c);
     if (!bytes || !size) throw std::runtime_error("null result");
+    k->host_payload();
     const std::vector<uint8_t> b = correction_write(k->data);
     *bytes = dup_bytes(b.data(), b.size());
     *size = b.size();
@@ -632,6 +634,33 @@ vnrAmdCorrection vnrAmdCreateCorrectionFromBytes(const void* bytes, size_t size)
     auto k = std::make_shared<Correction>();
     k->data = correction_parse(bytes, size);
     k->max_abs_before = std::numeric_limits<double>::quiet_NaN();   // known to the build alone; worst_after = -1, -1, -1 and the counts 0 likewise
+    return new vnrAmdCorrection_t{std::move(k)};
+  });
+}
+int vnrAmdCorrectionSerializePacked(vnrAmdCorrection c, void** bytes, size_t* size)
+{
+  return guarded([&]() {
+    Correction* k = as_correction(c);
+    if (!bytes || !size) throw std::runtime_error("null result");
+    if (!k->has_packed) {   // the device pack, once
+      if (!k->data.cells.empty() && !Runtime::get().ready()) Runtime::get().init(-1);
+      correction_packed_payload(*k, Runtime::get().stream);
+    }
+    const std::vector<uint8_t> b = correction_packed_write(k->data.h, k->data.cells, k->packed_payload);
+    *bytes = dup_bytes(b.data(), b.size());
+    *size = b.size();
+  });
+}
+vnrAmdCorrection vnrAmdCreateCorrectionFromPackedBytes(const void* bytes, size_t size)
+{
+  return guarded_new<vnrAmdCorrection_t>([&]() {
+    auto k = std::make_shared<Correction>();
+    CorrectionPacked p = correction_packed_parse(bytes, size);
+    k->data.h = p.h;
+    k->data.cells = std::move(p.cells);
+    k->packed_payload = std::move(p.payload);
+    k->has_packed = k->from_packed = true;
+    k->max_abs_before = std::numeric_limits<double>::quiet_NaN();   // as CreateCorrectionFromBytes
     return new vnrAmdCorrection_t{std::move(k)};
   });
 }

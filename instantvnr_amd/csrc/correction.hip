@@ -733,7 +733,7 @@ void NeuralVolume::decode_to_device_corrected(Correction& corr, const DeviceTarg
   if (!corr.uploaded) {
     const std::vector<CorrectionTableEntry> table = make_table(corr.data, correction_n_cells(dims));
     corr.d_table.upload(table.data(), table.size(), stream);
-    corr.d_payload.upload(corr.data.payload.data(), corr.data.payload.size(), stream);
+    correction_ensure_device_payload(corr, stream);   // correction_pack.hip: uploaded, or unpacked on the device from packed bytes
     VNR_HIP_CHECK(hipStreamSynchronize(stream));   // `table` goes out of scope
     corr.uploaded = true;
   }

@@ -10,6 +10,7 @@
 
 #include "common.h"
 #include "correction_format.h"
+#include "correction_packed_format.h"
 #include "json.h"
 #include "network.h"
 #include "ooc_sampler.h"
@@ -121,7 +122,23 @@ struct Correction {
   DeviceBuffer<uint8_t> d_payload{MemTag::Network};
   DeviceBuffer<CorrectionTableEntry> d_table{MemTag::Network};
   bool uploaded = false;
+  // The packed form (correction_packed_format.h, correction_pack.hip).  packed_payload: the group table and the planes, either what the
+  // correction was read from (from_packed) or the cached result of the device pack (a correction never changes).  A correction read
+  // from packed bytes has an empty data.payload until the host unpacks it (host_payload), and d_payload is unpacked on the device.
+  std::vector<uint8_t> packed_payload;
+  bool has_packed = false, from_packed = false;
+  bool payload_uploaded = false;   // d_payload holds the fixed-width payload although the table is not there yet (`uploaded` implies it)
+  const std::vector<uint8_t>& host_payload()   // data.payload, unpacked on the host at its first use
+  {
+    if (from_packed && data.payload.empty() && !data.cells.empty()) data.payload = correction_unpack(data.h, data.cells, packed_payload);
+    return data.payload;
+  }
 };
+
+// correction_pack.hip.  The fixed-width payload made resident in d_payload: uploaded, or (from_packed) unpacked from the packed payload on
+// the device; and the device pack into packed_payload, which makes the payload resident first.  Both have synchronised on return.
+void correction_ensure_device_payload(Correction& corr, hipStream_t stream);
+const std::vector<uint8_t>& correction_packed_payload(Correction& corr, hipStream_t stream);
 
 struct VolumeDesc {  // MultiVolume, instantvnr_types.h:40-56 (single timestep)
   vec3i dims{0, 0, 0};

@@ -24,6 +24,10 @@ ingest time are printed.
                          source's type and ghost layers (vnrAmdNeuralVolumeDecodeToDeviceCorrected).  Per step: the raw bytes, the
                          params.json bytes plus the correction's bytes and the ratio, the flagged cells, the largest error before
                          and after; both calls timed, beside ErrorAgainstDevice and DecodeToDevice on the same arrays
+  --packed               with --error-bound: the packed form of each step's correction as well (vnrAmdCorrectionSerializePacked,
+                         vnrAmdCreateCorrectionFromPackedBytes).  Per step: the packed bytes, the fixed-width bytes over them, the
+                         compressed bytes and the ratio with the packed form, the time of the device pack and of the first corrected
+                         decode of a correction read from the packed bytes (upload, unpack on the device, apply)
   --guided               error-guided batches instead of the series (vnrAmdNeuralVolumeGuideSamplingByError): ONE static field, the
                          synthetic blob field with plateaus at both ends, trained --steps-per-frame steps in all, twice with the same
                          seeds: once with the error map re-installed as sampling weights every --refresh-every steps, once with
@@ -46,7 +50,14 @@ decode_error_kernel and decode_error_final_kernel.
 
 The --error-bound times are host clocks around whole calls in the same way: "build" evaluates the network twice and brings the codes
 to the host, "apply" evaluates it once.  The kernels are correction_measure_kernel, correction_encode_kernel and
-correction_apply_kernel."""
+correction_apply_kernel.
+
+The --packed times are host clocks around whole calls too.  "pack" is one vnrAmdCorrectionSerializePacked call on the correction the
+build returned, whose codes are resident: two kernels, the cells' offsets through the host between them, the packed bytes brought to
+the host and copied out (the result is cached, so it is one measurement a step, after a warm-up on a copy of the correction).
+"packed_first_apply" is the first vnrAmdNeuralVolumeDecodeToDeviceCorrected of a correction just read from the packed bytes: the
+upload of the packed payload, the unpack kernel and the apply; each repeat reads the bytes anew (the host's validation is outside the
+clock).  The kernels are correction_pack_measure_kernel, correction_pack_planes_kernel and correction_unpack_kernel."""
 import argparse
 import json
 import os
@@ -121,7 +132,7 @@ def round_trip(neural, ptr, dtype, strides, dims, ghost, value_range, repeat, co
     return row
 
 
-def error_bound(neural, ptr, dtype, strides, dims, ghost, value_range, eps, repeat):
+def error_bound(neural, ptr, dtype, strides, dims, ghost, value_range, eps, repeat, packed=False):
     """-> the --error-bound columns of one step.  `ptr` is the step's own device array (the reference of the correction)."""
     def build():
         c = api.vnrNeuralVolumeBuildCorrection(neural, ptr, dtype, eps, strides, value_range)
@@ -147,6 +158,21 @@ def error_bound(neural, ptr, dtype, strides, dims, ghost, value_range, eps, repe
     row.update(plain_decode_ms=round(best, 4), plain_decode_median_ms=round(median, 4))
     _, best, median = timed(lambda: api.vnrNeuralVolumeErrorAgainstDevice(neural, ptr, dtype, strides, None, value_range), repeat, 1)
     row.update(error_report_ms=round(best, 4), error_report_median_ms=round(median, 4))
+    if packed:
+        fixed = corr.to_bytes()
+        warm = api.Correction.from_bytes(fixed)
+        warm.to_packed_bytes()
+        warm.release()
+        blob, best, _ = timed(corr.to_packed_bytes, 1)
+        row.update(packed_correction_bytes=len(blob), fixed_over_packed=round(len(fixed) / len(blob), 3), packed_compressed_bytes=n_params + len(blob),
+                   packed_ratio=round(raw / (n_params + len(blob)), 3), pack_ms=round(best, 4))
+        times = []
+        for _ in range(repeat):
+            fresh = api.Correction.from_packed_bytes(blob)
+            times.append(timed(lambda: api.vnrNeuralVolumeDecodeToDeviceCorrected(neural, fresh, out.ptr + first, strides), 1)[1])
+            last = fresh.to_bytes() == fixed if len(times) == repeat else None
+            fresh.release()
+        row.update(packed_first_apply_ms=round(min(times), 4), packed_first_apply_median_ms=round(statistics.median(times), 4), packed_unpacks_to_fixed=last)
     out.free()
     corr.release()
     return row
@@ -207,6 +233,7 @@ def main(argv=None):
     p.add_argument("--compare-host", action="store_true")
     p.add_argument("--round-trip", action="store_true")
     p.add_argument("--error-bound", type=float, default=None, metavar="EPS")
+    p.add_argument("--packed", action="store_true")
     p.add_argument("--guided", action="store_true")
     p.add_argument("--uniform-fraction", type=float, default=0.25)
     p.add_argument("--refresh-every", type=int, default=100)
@@ -218,6 +245,8 @@ def main(argv=None):
         p.error("--round-trip needs a trained network: --steps-per-frame > 0")
     if a.error_bound is not None and (not a.steps_per_frame or not a.error_bound >= 0.0 or a.error_bound == float("inf")):
         p.error("--error-bound needs a trained network (--steps-per-frame > 0) and a finite EPS >= 0")
+    if a.packed and a.error_bound is None:
+        p.error("--packed needs --error-bound EPS")
 
     api._lib.require_device()
     api.check(api.lib().vnrAmdInit(-1))
@@ -268,7 +297,7 @@ def main(argv=None):
             if a.round_trip:     # in data units: the range that was applied inverts the ingest
                 row.update(round_trip(neural, ptr, dtype, strides, dims, a.ghost, used, a.repeat, coords))
             if a.error_bound is not None:
-                row.update(error_bound(neural, ptr, dtype, strides, dims, a.ghost, used, a.error_bound, a.repeat))
+                row.update(error_bound(neural, ptr, dtype, strides, dims, a.ghost, used, a.error_bound, a.repeat, a.packed))
         d.free()
         for k in ("create_ms", "host_create_ms", "host_create_median_ms"):
             if k in row:

@@ -10,7 +10,8 @@ evaluation of the same fp16 parameters (fp64_network below): the HIP path may be
 network (twice that, for the maximum over samples or entries), never farther.  The first sweeps of 3000 + 2500 draws
 (profiles/r04_fuzz.txt) found fourteen draws past the fixed bars, every one of this kind (one sample of 1025) or sitting on a discontinuity of
 the FUNCTION: an output on its L1 target (the gradient is a sign), or a ReLU unit whose fp32 sum is within rounding of zero (the mask follows
-the order of the sum).  Targets and training coordinates are therefore drawn away from both (away_from_relu_kinks)."""
+the order of the sum).  Targets and training coordinates are therefore drawn away from both (away_from_relu_kinks).  The 2^-8 bar holds the
+independent oracle end to end; the inference kernel itself is held layer by layer, at rounding level, by tests/test_gpu_inference_stages.py."""
 import os
 
 import numpy as np

@@ -291,7 +291,8 @@ int    vnrAmdNeuralVolumeErrorAgainstDevice(vnrAmdVolume neural, const void* d_r
 /* AMD extension: error-bounded round trip.  BuildCorrection stores what the network missed: quantised residuals for exactly the
  * macrocells (16^3, the grid of vnrAmdVolumeGetMacrocell, ragged at the upper faces) in which some voxel of the whole-grid decode
  * misses the tolerance eps against the field d_ref; DecodeToDeviceCorrected decodes with that applied.  The pair (params.json,
- * serialised correction) is the compressed field.  The box is always the whole grid of the volume; pointer, strides, alignment,
+ * serialised correction) is the compressed field.  The build's box is always the whole grid of the volume, DecodeToDeviceCorrected's
+ * too; DecodeBoxToDeviceCorrected ("corrected decode of a box" below) takes any box of it.  Pointer, strides, alignment,
  * allocation room, stream and value range are those of DecodeToDevice, with its refusals and messages.
  *
  * Per voxel, dec is the typed value DecodeToDevice stores for this value type and range, ref the voxel of d_ref, eps a finite
@@ -369,6 +370,42 @@ void vnrAmdReleaseCorrection(vnrAmdCorrection);
  * Errors: a null handle, null arguments, malformed bytes; SerializePacked of a correction not read from packed bytes needs a device. */
 int  vnrAmdCorrectionSerializePacked(vnrAmdCorrection, void** bytes, size_t* size);    /* vnrAmdFreeHost */
 vnrAmdCorrection vnrAmdCreateCorrectionFromPackedBytes(const void* bytes, size_t size); /* host only; unpacked at first use */
+/* AMD extension: corrected decode of a box, and the resident form of a correction.
+ *
+ * DecodeBoxToDeviceCorrected is DecodeToDeviceCorrected for a box of the volume's own grid (a correction exists at its voxel
+ * centres only, so there is no grid_dims): box_lo / box_size as in DecodeToDevice, NULL / NULL = the whole grid, which stores what
+ * DecodeToDeviceCorrected stores.  d_out points at the first voxel of the box, strides are in elements, NULL = dense over
+ * box_size; layout, alignment, allocation room, overlap and stream rules, refusals and messages are DecodeToDevice's; value type
+ * and range are the correction's.  Only the box's voxels are evaluated by the network and only they are written; a voxel's cell
+ * and its index in the cell are those of its grid coordinate box_lo + ijk, so a box stores exactly the voxels the whole-grid call
+ * stores there, whatever the chunk size.  A correction without flagged cells gives the plain DecodeToDevice of the box.
+ *
+ * SetResidentForm chooses what the apply reads on the device.  FIXED (the default of every correction however it was made): a
+ * 16-byte entry per macrocell of the grid and the fixed-width payload; a correction read from packed bytes is unpacked into it
+ * by its first apply.  PACKED: the packed payload as it is serialised, plus an index computed on the host from the group table:
+ * 16 bytes per macrocell of the grid {the cell's first plane word, its first group} and 4 bytes per group {the group's first word
+ * inside its cell (at most 63 * 64), nbits}.  The apply then gathers a voxel's code from the planes: cell -> entry, li -> group
+ * li / 64 and lane li % 64, z = sum over b < nbits of ((plane word b >> lane) & 1) << b, kinds 0 and 1 q = (z >> 1) ^ -(z & 1),
+ * kind 2 z is the stored bit pattern; a group with nbits == 0 reads no plane word.  No unpacked copy is made, and what is stored
+ * is bit for bit what the FIXED form stores.
+ * A correction that holds nothing on the device only notes the form, and its first apply uploads that form alone: PACKED set
+ * before the first apply of a correction read from packed bytes never allocates the fixed-width payload on the device and never
+ * runs the unpack.  A correction that is resident is converted by the call itself, on the library's stream: to PACKED it is
+ * packed on the device if it has no packed form yet (cached, as by SerializePacked), the index is built and uploaded, and the
+ * fixed-width payload and its table are released after the stream has drained; to FIXED the planes are unpacked on the device and
+ * then released with the index.  Serialize, SerializePacked and GetInfo give the same bytes and values in either form.
+ * GetResidency: form; payload_device_bytes = the payload of the resident form; index_device_bytes = the PACKED form's index, cell
+ * entries included (0 in FIXED form); device_bytes = everything the correction holds on the device, FIXED's cell table included;
+ * on_device = device_bytes != 0.  All are 0 before the first upload and for a correction without flagged cells.  In PACKED form
+ * device_bytes = packed payload + 4 * groups + 16 * cells of the grid.
+ * Errors: those of DecodeToDeviceCorrected; a null handle or result; a form other than 0 or 1 (nothing changes). */
+#define VNR_AMD_CORRECTION_RESIDENT_FIXED  0
+#define VNR_AMD_CORRECTION_RESIDENT_PACKED 1
+typedef struct vnrAmdCorrectionResidency { int form, on_device; uint64_t device_bytes, payload_device_bytes, index_device_bytes; } vnrAmdCorrectionResidency;
+int  vnrAmdCorrectionSetResidentForm(vnrAmdCorrection, int form);
+int  vnrAmdCorrectionGetResidency(vnrAmdCorrection, vnrAmdCorrectionResidency*);
+int  vnrAmdNeuralVolumeDecodeBoxToDeviceCorrected(vnrAmdVolume neural, vnrAmdCorrection, void* d_out, const int64_t strides[3],
+                                                  const int box_lo[3], const int box_size[3], void* stream, int verify_params);
 /* hash-grid encode only (tcnn_impl_decoder.cu:177-230, column = level*F + f): fp16 [n][padded_width] */
 int    vnrAmdNeuralVolumeEncode(vnrAmdVolume, size_t n, const float* d_coords, uint16_t* d_features, void* stream);
 /* AMD extension: state of the brick image, the de-hashed inference copy of the hashed levels (csrc/network.h).  It is built

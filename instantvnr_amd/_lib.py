@@ -63,6 +63,11 @@ class CorrectionInfo(C.Structure):
                 ("max_abs_before", C.c_double), ("max_abs_after", C.c_double), ("worst_after", C.c_int * 3)]
 
 
+class CorrectionResidency(C.Structure):
+    _fields_ = [("form", C.c_int), ("on_device", C.c_int), ("device_bytes", C.c_uint64), ("payload_device_bytes", C.c_uint64),
+                ("index_device_bytes", C.c_uint64)]
+
+
 def declared_symbols():
     """every function name declared in include/vnr_amd.h"""
     text = open(HEADER).read()
@@ -258,6 +263,9 @@ def lib():
     sig("vnrAmdCorrectionSerializePacked", I, P, C.POINTER(P), C.POINTER(SZ))
     sig("vnrAmdCreateCorrectionFromPackedBytes", P, P, SZ)
     sig("vnrAmdNeuralVolumeDecodeToDeviceCorrected", I, P, P, P, I64P, P, I)
+    sig("vnrAmdNeuralVolumeDecodeBoxToDeviceCorrected", I, P, P, P, I64P, IP, IP, P, I)
+    sig("vnrAmdCorrectionSetResidentForm", I, P, I)
+    sig("vnrAmdCorrectionGetResidency", I, P, C.POINTER(CorrectionResidency))
     sig("vnrAmdReleaseCorrection", None, P)
     _lib = L
     return L

@@ -552,6 +552,23 @@ class Correction(_Handle):
         b = bytes(b)
         return cls(lib().vnrAmdCreateCorrectionFromPackedBytes(b, len(b)))
 
+    RESIDENT_FORMS = {"fixed": 0, "packed": 1}
+
+    def set_resident_form(self, form):
+        """what the apply reads on the device (include/vnr_amd.h, "resident form"): "fixed", the default, the fixed-width payload;
+        "packed", the bit planes as they are serialised plus an index.  The results are the same bit for bit."""
+        if form not in self.RESIDENT_FORMS:
+            raise VnrAmdError(f"resident form must be 'fixed' or 'packed', got {form!r}")
+        check(lib().vnrAmdCorrectionSetResidentForm(self.h, self.RESIDENT_FORMS[form]))
+
+    def residency(self):
+        """-> dict of vnrAmdCorrectionResidency; form as "fixed" / "packed", on_device as bool"""
+        e = _lib.CorrectionResidency()
+        check(lib().vnrAmdCorrectionGetResidency(self.h, C.byref(e)))
+        out = {k: getattr(e, k) for k, _ in _lib.CorrectionResidency._fields_}
+        out["form"], out["on_device"] = ("fixed", "packed")[e.form], bool(e.on_device)
+        return out
+
 
 def vnrNeuralVolumeBuildCorrection(v, d_ref, dtype, eps, strides=None, value_range=None, stream=None):
     """residual corrections for the macrocells where what vnrNeuralVolumeDecodeToDevice would store (same dtype and value_range, the
@@ -561,9 +578,10 @@ def vnrNeuralVolumeBuildCorrection(v, d_ref, dtype, eps, strides=None, value_ran
     return Correction(lib().vnrAmdNeuralVolumeBuildCorrection(v.h, p, t, s, lo, hi, float(eps), st))
 
 
-def vnrNeuralVolumeDecodeToDeviceCorrected(v, correction, d_ptr, strides=None, stream=None, verify_params=False):
-    """vnrNeuralVolumeDecodeToDevice of the whole grid with `correction` applied; value type and range are the correction's.
-    verify_params: refuse unless the volume's parameters hash to what the correction was built on."""
+def vnrNeuralVolumeDecodeToDeviceCorrected(v, correction, d_ptr, strides=None, stream=None, verify_params=False, box=None):
+    """vnrNeuralVolumeDecodeToDevice with `correction` applied, of the whole grid or of `box` = (lower, size) of the volume's own grid
+    (`d_ptr` is then the address of the box's first voxel, `strides` None dense over the box); value type and range are the
+    correction's.  verify_params: refuse unless the volume's parameters hash to what the correction was built on."""
     ptr = d_ptr.ptr if isinstance(d_ptr, DeviceArray) else d_ptr
     if not ptr:
         raise VnrAmdError("null device data")
@@ -573,6 +591,11 @@ def vnrNeuralVolumeDecodeToDeviceCorrected(v, correction, d_ptr, strides=None, s
         if len(sl) != 3 or min(sl) <= 0:
             raise VnrAmdError(f"strides must be three positive element strides (sx, sy, sz), got {strides!r}")
         s = (C.c_int64 * 3)(*sl)
+    if box is not None:
+        b_lo, b_size, _ = _box_args(box)
+        check(lib().vnrAmdNeuralVolumeDecodeBoxToDeviceCorrected(v.h, correction.h, C.c_void_p(ptr), s, b_lo, b_size, C.c_void_p(stream) if stream else None,
+                                                                 int(bool(verify_params))))
+        return
     check(lib().vnrAmdNeuralVolumeDecodeToDeviceCorrected(v.h, correction.h, C.c_void_p(ptr), s, C.c_void_p(stream) if stream else None, int(bool(verify_params))))
 
 

@@ -669,7 +669,36 @@ int vnrAmdNeuralVolumeDecodeToDeviceCorrected(vnrAmdVolume v, vnrAmdCorrection c
   return guarded([&]() {
     NeuralVolume* n = as_neural(v);
     Correction* k = as_correction(c);
-    n->decode_to_device_corrected(*k, DeviceTarget{d_out, k->data.h.value_type, strides, (hipStream_t)stream}, verify_params != 0);
+    n->decode_to_device_corrected(*k, DeviceTarget{d_out, k->data.h.value_type, strides, (hipStream_t)stream}, nullptr, nullptr, verify_params != 0);
+  });
+}
+int vnrAmdNeuralVolumeDecodeBoxToDeviceCorrected(vnrAmdVolume v, vnrAmdCorrection c, void* d_out, const int64_t strides[3], const int box_lo[3],
+                                                 const int box_size[3], void* stream, int verify_params)
+{
+  return guarded([&]() {
+    NeuralVolume* n = as_neural(v);
+    Correction* k = as_correction(c);
+    n->decode_to_device_corrected(*k, DeviceTarget{d_out, k->data.h.value_type, strides, (hipStream_t)stream}, box_lo, box_size, verify_params != 0);
+  });
+}
+int vnrAmdCorrectionSetResidentForm(vnrAmdCorrection c, int form)
+{
+  return guarded([&]() {
+    Correction* k = as_correction(c);
+    correction_set_resident_form(*k, form, Runtime::get().stream);   // (a correction that holds device memory has initialised the runtime)
+  });
+}
+int vnrAmdCorrectionGetResidency(vnrAmdCorrection c, vnrAmdCorrectionResidency* out)
+{
+  return guarded([&]() {
+    Correction* k = as_correction(c);
+    if (!out) throw std::runtime_error("null result");
+    *out = vnrAmdCorrectionResidency{};
+    out->form = k->resident_form;
+    out->payload_device_bytes = k->d_payload.bytes() + k->d_packed.bytes();
+    out->index_device_bytes = k->d_plane_cells.bytes() + k->d_plane_groups.bytes();
+    out->device_bytes = out->payload_device_bytes + out->index_device_bytes + k->d_table.bytes();
+    out->on_device = out->device_bytes != 0;
   });
 }
 void vnrAmdReleaseCorrection(vnrAmdCorrection c) { delete c; }

@@ -390,11 +390,14 @@ struct ApplyOp {
   Quantiser k;
   uint64_t bx, by;
   CellGrid g;
+  uint32_t ox, oy, oz;   // the box's lower corner: cell and local index are those of the grid coordinate
   TableReader table;
   const uint8_t* __restrict__ payload;
 
+  // x, y, z: the voxel in the box
   __device__ __forceinline__ T voxel(uint64_t i, uint32_t x, uint32_t y, uint32_t z)
   {
+    x += ox; y += oy; z += oz;
     const T dec = convert_value<T>(values[i - b], c);
     const CorrectionTableEntry& en = table.at(g.cell(x, y, z));
     if (en.offset == ~0ull) return dec;
@@ -434,10 +437,120 @@ struct ApplyOp {
 
 template <typename T>
 __global__ void __launch_bounds__(kBlock) correction_apply_kernel(T* __restrict__ dst, BoxLayout L, uint64_t b, uint64_t e, const float* __restrict__ values,
-                                                                  Conversion c, Quantiser k, CellGrid g, const CorrectionTableEntry* __restrict__ table,
-                                                                  const uint8_t* __restrict__ payload)
+                                                                  Conversion c, Quantiser k, CellGrid g, uint32_t ox, uint32_t oy, uint32_t oz,
+                                                                  const CorrectionTableEntry* __restrict__ table, const uint8_t* __restrict__ payload)
 {
-  ApplyOp<T> op{values, b, c, k, L.bx, L.by, g, TableReader{table}, payload};
+  ApplyOp<T> op{values, b, c, k, L.bx, L.by, g, ox, oy, oz, TableReader{table}, payload};
+  for_each_chunk_voxel<T>(dst, L, b, e, op);
+}
+
+// ---- the apply that reads the bit planes (correction_packed_format.h): the same walk, a voxel's code gathered from its group's planes ----
+// The index of correction_plane_index on the device: cells[cell] = {the cell's first plane word, its first group} (word0 = ~0: not
+// flagged), groups[group] = the group's first word inside its cell | nbits << 16.  Code li of a cell is lane li % 64 of its group
+// li / 64, and bit b of its z is bit `lane` of the group's plane word b: nbits loads of 8 bytes, none for a group of zeros.  The M
+// codes [li, li + M) of ONE group come out of one pass over its planes, which is what a 16-byte piece inside an x-row of a cell
+// needs (cx == 16: always; a ragged cell, a box that starts between pieces: voxel by voxel where the piece straddles).
+template <typename T>
+struct PlanesApplyOp {
+  using Z = typename BitsOf<T>::type;   // kinds 0 and 1: the z of a code of at most 4 bytes has at most 32 bits; kind 2: sizeof(T) bytes
+  const float* __restrict__ values;
+  uint64_t b;
+  Conversion c;
+  Quantiser k;
+  uint64_t bx, by;
+  CellGrid g;
+  uint32_t ox, oy, oz;
+  const Correction::PlaneCell* __restrict__ cells;
+  const uint32_t* __restrict__ groups;
+  const uint64_t* __restrict__ planes;
+  uint32_t cell = 0xffffffffu;   // the entry cached while a lane stays in one cell, as TableReader does
+  Correction::PlaneCell entry{~0ull, 0, 0};
+
+  __device__ __forceinline__ const Correction::PlaneCell& at(uint32_t cl)
+  {
+    if (cl != cell) { entry = cells[cl]; cell = cl; }
+    return entry;
+  }
+  // z of the codes [li, li + M) of a flagged cell; they lie in one group
+  template <int M>
+  __device__ __forceinline__ void read_codes(const Correction::PlaneCell& en, uint32_t li, Z (&z)[M]) const
+  {
+    const uint32_t gi = groups[en.group0 + (li >> 6)], nbits = gi >> 16, lane = li & 63u;
+    const uint64_t* __restrict__ w = planes + (en.word0 + (gi & 0xffffu));
+#pragma unroll
+    for (int j = 0; j < M; ++j) z[j] = 0;
+    for (uint32_t p = 0; p < nbits; ++p) {
+      const uint32_t bits = (uint32_t)(w[p] >> lane);   // (M <= 16 lanes from `lane` on)
+#pragma unroll
+      for (int j = 0; j < M; ++j) z[j] |= (Z)((bits >> j) & 1u) << p;
+    }
+  }
+  __device__ __forceinline__ T corrected(T dec, Z z) const
+  {
+    if constexpr (std::is_floating_point_v<T>) {
+      if (k.kind == kCorrectionVerbatim) {
+        T v;
+        __builtin_memcpy(&v, &z, sizeof(T));
+        return v;
+      }
+    }
+    const int64_t q = (int64_t)(z >> 1) ^ -(int64_t)(z & 1);
+    return corrected_value<T>(dec, q, k);
+  }
+  // x, y, z: the voxel in the grid
+  __device__ __forceinline__ T voxel(uint64_t i, uint32_t x, uint32_t y, uint32_t z)
+  {
+    const T dec = convert_value<T>(values[i - b], c);
+    const Correction::PlaneCell& en = at(g.cell(x, y, z));
+    if (en.word0 == ~0ull) return dec;
+    Z code[1];
+    read_codes<1>(en, g.local(x, y, z), code);
+    return corrected(dec, code[0]);
+  }
+  __device__ __forceinline__ void one(T* p, uint64_t i)
+  {
+    uint32_t x, y, z;
+    split_index(i, bx, by, x, y, z);
+    *p = voxel(i, ox + x, oy + y, oz + z);
+  }
+  __device__ __forceinline__ void piece(T* p, uint64_t i)
+  {
+    constexpr int N = PieceOf<T>::n;
+    Piece<T> pc;
+    uint32_t x, y, z;
+    split_index(i, bx, by, x, y, z);
+    const uint32_t gx = ox + x, gy = oy + y, gz = oz + z;
+    const uint32_t li = g.local(gx, gy, gz);
+    // the piece stays in its row of the box, in one cell and in one group of it: its codes are consecutive lanes of that group
+    if (x + N <= (uint32_t)bx && (gx >> 4) == ((gx + N - 1) >> 4) && (li >> 6) == ((li + N - 1) >> 6)) {
+      const float* v = values + (i - b);
+#pragma unroll
+      for (int j = 0; j < N; ++j) pc.v[j] = convert_value<T>(v[j], c);
+      const Correction::PlaneCell& en = at(g.cell(gx, gy, gz));
+      if (en.word0 != ~0ull) {
+        Z code[N];
+        read_codes<N>(en, li, code);
+#pragma unroll
+        for (int j = 0; j < N; ++j) pc.v[j] = corrected(pc.v[j], code[j]);
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < N; ++j) {
+        pc.v[j] = voxel(i + j, ox + x, oy + y, oz + z);
+        if (++x == (uint32_t)bx) { x = 0; if (++y == (uint32_t)by) { y = 0; ++z; } }
+      }
+    }
+    *reinterpret_cast<Piece<T>*>(p) = pc;   // one 16-byte vector store
+  }
+};
+
+template <typename T>
+__global__ void __launch_bounds__(kBlock) correction_apply_planes_kernel(T* __restrict__ dst, BoxLayout L, uint64_t b, uint64_t e, const float* __restrict__ values,
+                                                                         Conversion c, Quantiser k, CellGrid g, uint32_t ox, uint32_t oy, uint32_t oz,
+                                                                         const Correction::PlaneCell* __restrict__ cells, const uint32_t* __restrict__ groups,
+                                                                         const uint64_t* __restrict__ planes)
+{
+  PlanesApplyOp<T> op{values, b, c, k, L.bx, L.by, g, ox, oy, oz, cells, groups, planes};
   for_each_chunk_voxel<T>(dst, L, b, e, op);
 }
 
@@ -471,19 +584,30 @@ void require_room(const void* p, size_t bytes, const char* what)
     throw std::runtime_error(std::string(what) + " spans " + std::to_string(bytes) + " bytes from its device pointer, the allocation has " + std::to_string(room) + " left");
 }
 
-// everything decode.hip refuses a whole-grid array for, with its messages; returns the layout of the grid in the caller's array
-BoxLayout validate_grid_array(const void* data, int type, const int64_t* strides, vec3i grid, float range_lo, float range_hi)
+std::string str3(const int v[3]) { return std::to_string(v[0]) + " x " + std::to_string(v[1]) + " x " + std::to_string(v[2]); }
+
+// everything decode.hip refuses a box of the grid in the caller's array for, with its messages (box_lo = box_size = null: the whole
+// grid); returns the layout of the box in the caller's array and its lower corner
+BoxLayout validate_box_array(const void* data, int type, const int64_t* strides, const int box_lo[3], const int box_size[3], vec3i grid, vec3i& lower, float range_lo,
+                             float range_hi)
 {
   if (!data) throw std::runtime_error("null device data");
   const size_t ts = device_value_type_size(type);   // refuses the 64-bit integer and the vector types like the ingest
   if (grid.x <= 0 || grid.y <= 0 || grid.z <= 0)
     throw std::runtime_error("grid dimensions must be positive: " + std::to_string(grid.x) + " x " + std::to_string(grid.y) + " x " + std::to_string(grid.z));
+  if ((box_lo == nullptr) != (box_size == nullptr)) throw std::runtime_error("box_lo and box_size go together: both or neither");
+  lower = box_lo ? vec3i{box_lo[0], box_lo[1], box_lo[2]} : vec3i{0, 0, 0};
+  const vec3i size = box_size ? vec3i{box_size[0], box_size[1], box_size[2]} : grid;
+  if (size.x <= 0 || size.y <= 0 || size.z <= 0) throw std::runtime_error("box sizes must be positive: " + str3(box_size));
+  if (lower.x < 0 || lower.y < 0 || lower.z < 0 || (int64_t)lower.x + size.x > grid.x || (int64_t)lower.y + size.y > grid.y || (int64_t)lower.z + size.z > grid.z)
+    throw std::runtime_error("the box (lower " + str3(box_lo) + ", size " + str3(box_size) + ") is outside the grid " + std::to_string(grid.x) + " x " +
+                             std::to_string(grid.y) + " x " + std::to_string(grid.z));
   const bool integer = type != 8 && type != 12;
   if (!(range_lo < range_hi) && !(range_lo > range_hi)) throw std::runtime_error("range_lo == range_hi (or a NaN): an empty value range");
   if (integer && range_lo > range_hi) throw std::runtime_error("an integer value type needs a value range (range_lo < range_hi)");
 
   BoxLayout L{};
-  L.bx = (uint64_t)grid.x; L.by = (uint64_t)grid.y; L.bz = (uint64_t)grid.z;
+  L.bx = (uint64_t)size.x; L.by = (uint64_t)size.y; L.bz = (uint64_t)size.z;
   L.sx = strides ? strides[0] : 1;
   L.sy = strides ? strides[1] : (int64_t)L.bx;
   L.sz = strides ? strides[2] : (int64_t)(L.bx * L.by);
@@ -510,7 +634,7 @@ BoxLayout validate_grid_array(const void* data, int type, const int64_t* strides
 
   L.gather = L.sx != 1;
   if (!L.gather) {
-    // contiguous runs: the whole grid, whole slices, or x-rows
+    // contiguous runs: the whole box, whole slices, or x-rows
     if (L.sy == (int64_t)L.bx && L.sz == (int64_t)(L.bx * L.by)) { L.run_len = L.bx * L.by * L.bz; L.runs_y = 1; L.sy = 0; L.sz = 0; }
     else if (L.sy == (int64_t)L.bx) { L.run_len = L.bx * L.by; L.runs_y = 1; L.sy = 0; }
     else { L.run_len = L.bx; L.runs_y = L.by; }
@@ -606,10 +730,10 @@ std::shared_ptr<Correction> NeuralVolume::build_correction(const DeviceSource& r
   if (!net_.valid()) throw std::runtime_error("neural volume has no valid network");
   if (!(eps >= 0.0) || !std::isfinite(eps)) throw std::runtime_error("eps must be a finite tolerance >= 0 in data units, got " + std::to_string(eps));
   const vec3i grid = desc.dims;
-  const BoxLayout L = validate_grid_array(ref.data, ref.type, ref.strides, grid, range_lo, range_hi);
+  vec3i lower;
+  const BoxLayout L = validate_box_array(ref.data, ref.type, ref.strides, nullptr, nullptr, grid, lower, range_lo, range_hi);
   const uint64_t total = L.bx * L.by * L.bz, chunk = std::min(chunk_samples(), total);
   const vec3f rdims = {1.0f / (float)grid.x, 1.0f / (float)grid.y, 1.0f / (float)grid.z};
-  const vec3i lower{0, 0, 0};
   const Conversion c{range_lo, range_hi - range_lo, range_lo < range_hi};
   const bool is_float = correction_type_is_float(ref.type);
   const uint32_t kind = !is_float ? kCorrectionInteger : (eps > 0.0 ? kCorrectionFloat : kCorrectionVerbatim);
@@ -710,7 +834,63 @@ std::shared_ptr<Correction> NeuralVolume::build_correction(const DeviceSource& r
   return corr;
 }
 
-void NeuralVolume::decode_to_device_corrected(Correction& corr, const DeviceTarget& out, bool verify_params)
+void correction_make_resident(Correction& corr, hipStream_t stream)
+{
+  const CorrectionData& d = corr.data;
+  if (d.cells.empty()) return;
+  const uint64_t n_cells = correction_n_cells(d.h.dims);
+  if (corr.resident_form == 0) {
+    if (!corr.uploaded) {
+      const std::vector<CorrectionTableEntry> table = make_table(d, n_cells);
+      corr.d_table.upload(table.data(), table.size(), stream);
+      correction_ensure_device_payload(corr, stream);   // correction_pack.hip: uploaded, or unpacked on the device from the packed payload
+      VNR_HIP_CHECK(hipStreamSynchronize(stream));   // `table` goes out of scope
+      corr.uploaded = true;
+    }
+    if (corr.planes_uploaded) {
+      VNR_HIP_CHECK(hipStreamSynchronize(stream));   // no apply still reads the planes
+      corr.d_packed.release(); corr.d_plane_cells.release(); corr.d_plane_groups.release();
+      corr.planes_uploaded = false;
+    }
+    return;
+  }
+  if (!corr.planes_uploaded) {
+    const std::vector<uint8_t>& packed = correction_packed_payload(corr, stream);   // (the device pack, once, of a correction that has no packed form yet)
+    const CorrectionPlaneIndex ix = correction_plane_index(d.h, d.cells, packed);
+    if (ix.group_word.size() > 0xffffffffull) throw std::runtime_error("the correction has more than 2^32 groups");
+    std::vector<Correction::PlaneCell> cells(n_cells, Correction::PlaneCell{~0ull, 0, 0});
+    for (size_t i = 0; i < d.cells.size(); ++i) cells[d.cells[i].cell] = Correction::PlaneCell{ix.cell_word0[i], (uint32_t)ix.cell_group0[i], 0};
+    std::vector<uint32_t> groups(ix.group_word.size());
+    for (size_t g = 0; g < groups.size(); ++g) groups[g] = (uint32_t)ix.group_word[g] | (uint32_t)packed[g] << 16;
+    corr.d_plane_cells.upload(cells.data(), cells.size(), stream);
+    corr.d_plane_groups.upload(groups.data(), groups.size(), stream);
+    corr.d_packed.upload(packed.data(), packed.size(), stream);   // as it is (hipMalloc aligns it; the planes start at a multiple of 8)
+    VNR_HIP_CHECK(hipStreamSynchronize(stream));   // the host vectors go out of scope
+    corr.planes_uploaded = true;
+  }
+  if (corr.uploaded || corr.payload_uploaded) {
+    VNR_HIP_CHECK(hipStreamSynchronize(stream));   // no apply or pack still reads the fixed-width payload
+    corr.d_payload.release(); corr.d_table.release();
+    corr.uploaded = corr.payload_uploaded = false;
+  }
+}
+
+void correction_set_resident_form(Correction& corr, int form, hipStream_t stream)
+{
+  if (form != 0 && form != 1) throw std::runtime_error("unknown resident form " + std::to_string(form) + " (0: fixed-width, 1: packed)");
+  if (form == corr.resident_form) return;
+  const int before = corr.resident_form;
+  corr.resident_form = form;
+  if (!corr.uploaded && !corr.payload_uploaded && !corr.planes_uploaded) return;   // nothing on the device yet: the first apply brings this form
+  try {
+    correction_make_resident(corr, stream);
+  } catch (...) {
+    corr.resident_form = before;
+    throw;
+  }
+}
+
+void NeuralVolume::decode_to_device_corrected(Correction& corr, const DeviceTarget& out, const int box_lo[3], const int box_size[3], bool verify_params)
 {
   if (!net_.valid()) throw std::runtime_error("neural volume has no valid network");
   const CorrectionHeader& h = corr.data.h;
@@ -718,7 +898,8 @@ void NeuralVolume::decode_to_device_corrected(Correction& corr, const DeviceTarg
   if (h.dims[0] != grid.x || h.dims[1] != grid.y || h.dims[2] != grid.z)
     throw std::runtime_error("the correction's dims (" + std::to_string(h.dims[0]) + " x " + std::to_string(h.dims[1]) + " x " + std::to_string(h.dims[2]) +
                              ") differ from the volume's (" + std::to_string(grid.x) + " x " + std::to_string(grid.y) + " x " + std::to_string(grid.z) + ")");
-  const BoxLayout L = validate_grid_array(out.data, h.value_type, out.strides, grid, h.range_lo, h.range_hi);
+  vec3i lower;
+  const BoxLayout L = validate_box_array(out.data, h.value_type, out.strides, box_lo, box_size, grid, lower, h.range_lo, h.range_hi);
   const uint64_t chunk_limit = chunk_samples();
   if (verify_params) {
     if (h.n_params != (uint64_t)net_.n_params())
@@ -726,20 +907,13 @@ void NeuralVolume::decode_to_device_corrected(Correction& corr, const DeviceTarg
     if (h.params_hash != params_hash()) throw std::runtime_error("the volume's parameters are not the ones the correction was built on (their hash differs)");
   }
   if (corr.data.cells.empty()) {   // nothing to apply: the plain decode
-    decode_to_device(DeviceTarget{out.data, h.value_type, out.strides, out.consumer}, nullptr, nullptr, nullptr, h.range_lo, h.range_hi);
+    decode_to_device(DeviceTarget{out.data, h.value_type, out.strides, out.consumer}, box_lo, box_size, nullptr, h.range_lo, h.range_hi);
     return;
   }
-  const int dims[3] = {grid.x, grid.y, grid.z};
-  if (!corr.uploaded) {
-    const std::vector<CorrectionTableEntry> table = make_table(corr.data, correction_n_cells(dims));
-    corr.d_table.upload(table.data(), table.size(), stream);
-    correction_ensure_device_payload(corr, stream);   // correction_pack.hip: uploaded, or unpacked on the device from packed bytes
-    VNR_HIP_CHECK(hipStreamSynchronize(stream));   // `table` goes out of scope
-    corr.uploaded = true;
-  }
+  correction_make_resident(corr, stream);
   const uint64_t total = L.bx * L.by * L.bz, chunk = std::min(chunk_limit, total);
   const vec3f rdims = {1.0f / (float)grid.x, 1.0f / (float)grid.y, 1.0f / (float)grid.z};
-  const vec3i lower{0, 0, 0};
+  const uint32_t ox = (uint32_t)lower.x, oy = (uint32_t)lower.y, oz = (uint32_t)lower.z;
   const Conversion c{h.range_lo, h.range_hi - h.range_lo, h.range_lo < h.range_hi};
   const Quantiser k = make_quantiser(h.kind, h.eps);
   const CellGrid g = make_cell_grid(grid);
@@ -753,11 +927,15 @@ void NeuralVolume::decode_to_device_corrected(Correction& corr, const DeviceTarg
     const uint32_t blocks = chunk_grid(L, h.value_type, b, e);
     dispatch_type(h.value_type, [&](auto* tag) {
       using T = std::remove_pointer_t<decltype(tag)>;
-      correction_apply_kernel<T><<<blocks, kBlock, 0, stream>>>((T*)out.data, L, b, e, dd_values_.ptr, c, k, g, corr.d_table.ptr, corr.d_payload.ptr);
+      if (corr.resident_form == 0)
+        correction_apply_kernel<T><<<blocks, kBlock, 0, stream>>>((T*)out.data, L, b, e, dd_values_.ptr, c, k, g, ox, oy, oz, corr.d_table.ptr, corr.d_payload.ptr);
+      else
+        correction_apply_planes_kernel<T><<<blocks, kBlock, 0, stream>>>((T*)out.data, L, b, e, dd_values_.ptr, c, k, g, ox, oy, oz, corr.d_plane_cells.ptr,
+                                                                         corr.d_plane_groups.ptr, corr.d_planes());
     });
     VNR_HIP_CHECK(hipGetLastError());
   }
-  VNR_HIP_CHECK(hipStreamSynchronize(stream));   // on return the grid is there
+  VNR_HIP_CHECK(hipStreamSynchronize(stream));   // on return the box is there
 }
 
 }  // namespace vnr

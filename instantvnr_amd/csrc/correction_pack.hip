@@ -178,10 +178,12 @@ void unpack_on_device(Correction& corr, hipStream_t stream)
   DeviceBuffer<uint8_t> d_packed(MemTag::Network);
   d_cells.upload(cells.data(), cells.size(), stream);
   d_word0.upload(word0.data(), word0.size(), stream);
-  d_packed.upload(corr.packed_payload.data(), corr.packed_payload.size(), stream);   // as it is (hipMalloc aligns it; the planes start at a multiple of 8)
+  // as it is (hipMalloc aligns it; the planes start at a multiple of 8), unless the planes are resident already (the packed resident form)
+  if (!corr.planes_uploaded) d_packed.upload(corr.packed_payload.data(), corr.packed_payload.size(), stream);
+  const uint8_t* packed = corr.planes_uploaded ? corr.d_packed.ptr : d_packed.ptr;
   corr.d_payload.resize(correction_fixed_payload_bytes(d.h, d.cells));
   corr.d_payload.zero(stream);
-  correction_unpack_kernel<<<cell_blocks(cells.size()), kWave, 0, stream>>>(d_packed.ptr, reinterpret_cast<const uint64_t*>(d_packed.ptr + table_bytes), d_cells.ptr, d_word0.ptr,
+  correction_unpack_kernel<<<cell_blocks(cells.size()), kWave, 0, stream>>>(packed, reinterpret_cast<const uint64_t*>(packed + table_bytes), d_cells.ptr, d_word0.ptr,
                                                                              (uint32_t)cells.size(), d.h.kind == kCorrectionVerbatim, corr.d_payload.ptr);
   VNR_HIP_CHECK(hipGetLastError());
   VNR_HIP_CHECK(hipStreamSynchronize(stream));   // the host vectors and the packed copy go out of scope
@@ -192,7 +194,7 @@ void unpack_on_device(Correction& corr, hipStream_t stream)
 void correction_ensure_device_payload(Correction& corr, hipStream_t stream)
 {
   if (corr.uploaded || corr.payload_uploaded || corr.data.cells.empty()) return;
-  if (corr.from_packed) {
+  if (corr.from_packed || corr.planes_uploaded) {
     unpack_on_device(corr, stream);
   } else {
     corr.d_payload.upload(corr.data.payload.data(), corr.data.payload.size(), stream);

@@ -195,4 +195,30 @@ std::vector<uint8_t> correction_unpack(const CorrectionHeader& h, const std::vec
   return out;
 }
 
+CorrectionPlaneIndex correction_plane_index(const CorrectionHeader& h, const std::vector<CorrectionCellEntry>& cells, const std::vector<uint8_t>& packed_payload)
+{
+  CorrectionPlaneIndex ix;
+  const uint64_t n_groups = correction_n_groups(h, cells), table_bytes = correction_group_table_bytes(n_groups);
+  if (packed_payload.size() < table_bytes) throw std::runtime_error("the packed payload is shorter than its group table");
+  ix.cell_group0.reserve(cells.size());
+  ix.cell_word0.reserve(cells.size());
+  ix.group_word.reserve(n_groups);
+  const uint8_t* table = packed_payload.data();
+  uint64_t g = 0;
+  for (const CorrectionCellEntry& e : cells) {
+    const uint64_t groups = correction_cell_groups(correction_cell_voxels(h.dims, e.cell));
+    ix.cell_group0.push_back(g);
+    ix.cell_word0.push_back(ix.n_words);
+    uint32_t in_cell = 0;   // at most 64 groups of at most 64 planes
+    for (uint64_t k = 0; k < groups; ++k, ++g) {
+      if (table[g] > kCorrectionGroup) throw std::runtime_error("nbits " + std::to_string(table[g]) + " of group " + std::to_string(g) + " exceeds 64");
+      ix.group_word.push_back((uint16_t)in_cell);
+      in_cell += table[g];
+    }
+    ix.n_words += in_cell;
+  }
+  if (packed_payload.size() - table_bytes != 8 * ix.n_words) throw std::runtime_error("the packed payload does not have the size its group table gives");
+  return ix;
+}
+
 }  // namespace vnr

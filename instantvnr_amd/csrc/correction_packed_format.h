@@ -37,4 +37,16 @@ CorrectionPacked correction_packed_parse(const void* bytes, size_t size);
 // the fixed-width payload (correction_format.h) of a packed payload that correction_packed_parse accepted; the cells' padding is zero
 std::vector<uint8_t> correction_unpack(const CorrectionHeader& h, const std::vector<CorrectionCellEntry>& cells, const std::vector<uint8_t>& packed_payload);
 
+// Where a code lies in the planes, for a reader that starts at a voxel (the apply that reads the planes, correction.hip): code li of
+// flagged cell i is lane li % 64 of group cell_group0[i] + li / 64, whose nbits plane words start at word
+// cell_word0[i] + group_word[that group] of the planes.
+struct CorrectionPlaneIndex {
+  std::vector<uint64_t> cell_group0, cell_word0;   // per flagged cell: the groups and the plane words in front of it
+  std::vector<uint16_t> group_word;                // per group: the plane words of its cell in front of it, at most 63 * 64
+  uint64_t n_words = 0;                            // plane words in all
+};
+// of a packed payload that correction_packed_parse accepted or the device pack made; throws if the payload's size is not the one its
+// group table gives
+CorrectionPlaneIndex correction_plane_index(const CorrectionHeader& h, const std::vector<CorrectionCellEntry>& cells, const std::vector<uint8_t>& packed_payload);
+
 }  // namespace vnr

@@ -128,6 +128,16 @@ struct Correction {
   std::vector<uint8_t> packed_payload;
   bool has_packed = false, from_packed = false;
   bool payload_uploaded = false;   // d_payload holds the fixed-width payload although the table is not there yet (`uploaded` implies it)
+  // The resident form (vnrAmdCorrectionSetResidentForm): what the apply reads on the device.  0, fixed: d_table and d_payload above.
+  // 1, packed: the packed payload as it is serialised and the index correction_plane_index gives, {first plane word, first group} for
+  // every cell of the grid and {first word inside the cell, nbits} for every group; d_table and d_payload are then released.
+  struct PlaneCell { uint64_t word0; uint32_t group0, pad; };   // word0 = ~0: the cell is not flagged
+  int resident_form = 0;
+  DeviceBuffer<uint8_t> d_packed{MemTag::Network};
+  DeviceBuffer<PlaneCell> d_plane_cells{MemTag::Network};
+  DeviceBuffer<uint32_t> d_plane_groups{MemTag::Network};   // word | nbits << 16
+  bool planes_uploaded = false;
+  const uint64_t* d_planes() const { return reinterpret_cast<const uint64_t*>(d_packed.ptr + correction_group_table_bytes(d_plane_groups.count)); }
   const std::vector<uint8_t>& host_payload()   // data.payload, unpacked on the host at its first use
   {
     if (from_packed && data.payload.empty() && !data.cells.empty()) data.payload = correction_unpack(data.h, data.cells, packed_payload);
@@ -135,10 +145,16 @@ struct Correction {
   }
 };
 
-// correction_pack.hip.  The fixed-width payload made resident in d_payload: uploaded, or (from_packed) unpacked from the packed payload on
-// the device; and the device pack into packed_payload, which makes the payload resident first.  Both have synchronised on return.
+// correction_pack.hip.  The fixed-width payload made resident in d_payload: uploaded, or (from_packed, or with the planes resident)
+// unpacked from the packed payload on the device; and the device pack into packed_payload, which makes the payload resident first.
+// Both have synchronised on return.
 void correction_ensure_device_payload(Correction& corr, hipStream_t stream);
 const std::vector<uint8_t>& correction_packed_payload(Correction& corr, hipStream_t stream);
+// What the apply of corr.resident_form reads made resident, and what only the other form reads released once the stream has drained.
+// Has synchronised on return.  A correction without a flagged cell holds nothing.
+void correction_make_resident(Correction& corr, hipStream_t stream);
+// vnrAmdCorrectionSetResidentForm: a correction that holds nothing on the device only notes the form, any other is converted at once
+void correction_set_resident_form(Correction& corr, int form, hipStream_t stream);
 
 struct VolumeDesc {  // MultiVolume, instantvnr_types.h:40-56 (single timestep)
   vec3i dims{0, 0, 0};
@@ -290,10 +306,11 @@ public:
   // Error-bounded round trip (correction.hip; no reference counterpart; the arithmetic is spelled out in include/vnr_amd.h).
   // build_correction: quantised residuals of exactly the macrocells where some voxel of the whole-grid decode (value type of `ref`,
   // this range) misses `eps` against `ref`; two chunked passes, the network evaluated in each, no full-size intermediate.
-  // decode_to_device_corrected: decode_to_device of the whole grid with the correction applied (type and range are the correction's;
-  // out.type is ignored).  verify_params: refuse unless the parameters hash to what the correction was built on.
+  // decode_to_device_corrected: decode_to_device of a box of the volume's own grid (box_lo = box_size = null: the whole grid) with the
+  // correction applied, in whichever form is resident (type and range are the correction's; out.type is ignored); only the box's
+  // voxels are evaluated.  verify_params: refuse unless the parameters hash to what the correction was built on.
   std::shared_ptr<Correction> build_correction(const DeviceSource& ref, float range_lo, float range_hi, double eps);
-  void decode_to_device_corrected(Correction& corr, const DeviceTarget& out, bool verify_params);
+  void decode_to_device_corrected(Correction& corr, const DeviceTarget& out, const int box_lo[3], const int box_size[3], bool verify_params);
   uint64_t params_hash();   // FNV-1a 64 of the fp16 parameter blob
   // network.cu:328-365 / :367-405: raw fp32, z-slice by z-slice, every slice padded to a multiple of 256 values
   void save_inference_volume(const std::string& filename);

@@ -28,6 +28,13 @@ ingest time are printed.
                          vnrAmdCreateCorrectionFromPackedBytes).  Per step: the packed bytes, the fixed-width bytes over them, the
                          compressed bytes and the ratio with the packed form, the time of the device pack and of the first corrected
                          decode of a correction read from the packed bytes (upload, unpack on the device, apply)
+  --resident FORM        with --error-bound: fixed | packed, the resident form of each step's correction, set before the corrected
+                         decode (vnrAmdCorrectionSetResidentForm); packed keeps the bit planes and an index on the device and no
+                         fixed-width payload.  Per step: the form and the bytes the correction holds on the device     [fixed]
+  --roi x0,y0,z0,sx,sy,sz  with --error-bound: additionally decode that box of the grid corrected into a dense device array
+                         (vnrAmdNeuralVolumeDecodeBoxToDeviceCorrected), check it on the host against the step's own array (every
+                         voxel within max_abs_after) and against the same box cut out of the whole-grid corrected decode (equal
+                         bytes), and time it beside the plain vnrAmdNeuralVolumeDecodeToDevice of the box
   --guided               error-guided batches instead of the series (vnrAmdNeuralVolumeGuideSamplingByError): ONE static field, the
                          synthetic blob field with plateaus at both ends, trained --steps-per-frame steps in all, twice with the same
                          seeds: once with the error map re-installed as sampling weights every --refresh-every steps, once with
@@ -57,7 +64,12 @@ build returned, whose codes are resident: two kernels, the cells' offsets throug
 the host and copied out (the result is cached, so it is one measurement a step, after a warm-up on a copy of the correction).
 "packed_first_apply" is the first vnrAmdNeuralVolumeDecodeToDeviceCorrected of a correction just read from the packed bytes: the
 upload of the packed payload, the unpack kernel and the apply; each repeat reads the bytes anew (the host's validation is outside the
-clock).  The kernels are correction_pack_measure_kernel, correction_pack_planes_kernel and correction_unpack_kernel."""
+clock).  The kernels are correction_pack_measure_kernel, correction_pack_planes_kernel and correction_unpack_kernel.  With
+--resident packed the form is set on the fresh correction first: the upload of the packed payload and of the index, and the apply
+that reads the planes (correction_apply_planes_kernel); no unpack.
+
+The --roi times are host clocks around whole calls as well, each warmed up once: "roi_apply" evaluates the network for the box's
+voxels alone and applies the correction in the resident form, "roi_plain_decode" is DecodeToDevice of the same box."""
 import argparse
 import json
 import os
@@ -132,8 +144,9 @@ def round_trip(neural, ptr, dtype, strides, dims, ghost, value_range, repeat, co
     return row
 
 
-def error_bound(neural, ptr, dtype, strides, dims, ghost, value_range, eps, repeat, packed=False):
-    """-> the --error-bound columns of one step.  `ptr` is the step's own device array (the reference of the correction)."""
+def error_bound(neural, ptr, dtype, strides, dims, ghost, value_range, eps, repeat, packed=False, resident="fixed", roi=None, step=None):
+    """-> the --error-bound columns of one step.  `ptr` is the step's own device array (the reference of the correction), `step`
+    the same voxels on the host (for --roi)."""
     def build():
         c = api.vnrNeuralVolumeBuildCorrection(neural, ptr, dtype, eps, strides, value_range)
         held.append(c)
@@ -152,8 +165,22 @@ def error_bound(neural, ptr, dtype, strides, dims, ghost, value_range, eps, repe
     padded = tuple(d + 2 * ghost for d in dims)
     out = api.DeviceArray((padded[2], padded[1], padded[0]), dtype)
     first = (ghost + ghost * padded[0] + ghost * padded[0] * padded[1]) * dtype.itemsize
+    corr.set_resident_form(resident)      # (the build left the fixed-width codes resident: packed converts them here, once)
     _, best, median = timed(lambda: api.vnrNeuralVolumeDecodeToDeviceCorrected(neural, corr, out.ptr + first, strides), repeat, 1)
-    row.update(apply_ms=round(best, 4), apply_median_ms=round(median, 4))
+    row.update(apply_ms=round(best, 4), apply_median_ms=round(median, 4), resident=resident, device_bytes=corr.residency()["device_bytes"])
+    if roi is not None:
+        lo, size = roi
+        whole = out.numpy()[ghost:ghost + dims[2], ghost:ghost + dims[1], ghost:ghost + dims[0]]
+        cut = tuple(slice(lo[a], lo[a] + size[a]) for a in (2, 1, 0))
+        box = api.DeviceArray((size[2], size[1], size[0]), dtype)
+        _, best, median = timed(lambda: api.vnrNeuralVolumeDecodeToDeviceCorrected(neural, corr, box, box=roi), repeat, 1)
+        got = box.numpy()
+        worst = float(np.abs(got.astype(np.float64) - step[cut].astype(np.float64)).max())
+        row.update(roi=list(lo) + list(size), roi_apply_ms=round(best, 4), roi_apply_median_ms=round(median, 4), roi_max_abs_error=worst,
+                   roi_within_bound=bool(worst <= info["max_abs_after"]), roi_equals_whole_grid=bool(np.array_equal(got.view(np.uint8), np.ascontiguousarray(whole[cut]).view(np.uint8))))
+        _, best, median = timed(lambda: api.vnrNeuralVolumeDecodeToDevice(neural, box, dtype, None, roi, None, value_range), repeat, 1)
+        row.update(roi_plain_decode_ms=round(best, 4), roi_plain_decode_median_ms=round(median, 4))
+        box.free()
     _, best, median = timed(lambda: api.vnrNeuralVolumeDecodeToDevice(neural, out.ptr + first, dtype, strides, None, None, value_range), repeat, 1)
     row.update(plain_decode_ms=round(best, 4), plain_decode_median_ms=round(median, 4))
     _, best, median = timed(lambda: api.vnrNeuralVolumeErrorAgainstDevice(neural, ptr, dtype, strides, None, value_range), repeat, 1)
@@ -169,6 +196,7 @@ def error_bound(neural, ptr, dtype, strides, dims, ghost, value_range, eps, repe
         times = []
         for _ in range(repeat):
             fresh = api.Correction.from_packed_bytes(blob)
+            fresh.set_resident_form(resident)
             times.append(timed(lambda: api.vnrNeuralVolumeDecodeToDeviceCorrected(neural, fresh, out.ptr + first, strides), 1)[1])
             last = fresh.to_bytes() == fixed if len(times) == repeat else None
             fresh.release()
@@ -234,6 +262,8 @@ def main(argv=None):
     p.add_argument("--round-trip", action="store_true")
     p.add_argument("--error-bound", type=float, default=None, metavar="EPS")
     p.add_argument("--packed", action="store_true")
+    p.add_argument("--resident", default="fixed", choices=["fixed", "packed"])
+    p.add_argument("--roi", default=None, metavar="x0,y0,z0,sx,sy,sz")
     p.add_argument("--guided", action="store_true")
     p.add_argument("--uniform-fraction", type=float, default=0.25)
     p.add_argument("--refresh-every", type=int, default=100)
@@ -247,6 +277,18 @@ def main(argv=None):
         p.error("--error-bound needs a trained network (--steps-per-frame > 0) and a finite EPS >= 0")
     if a.packed and a.error_bound is None:
         p.error("--packed needs --error-bound EPS")
+    roi = None
+    if a.roi is not None or a.resident != "fixed":
+        if a.error_bound is None:
+            p.error("--resident and --roi need --error-bound EPS")
+    if a.roi is not None:
+        try:
+            v = [int(x) for x in a.roi.split(",")]
+        except ValueError:
+            v = []
+        if len(v) != 6 or min(v[:3]) < 0 or min(v[3:]) <= 0 or any(v[k] + v[3 + k] > a.size for k in range(3)):
+            p.error(f"--roi needs x0,y0,z0,sx,sy,sz: a box with positive sizes inside the {a.size}^3 grid")
+        roi = (tuple(v[:3]), tuple(v[3:]))
 
     api._lib.require_device()
     api.check(api.lib().vnrAmdInit(-1))
@@ -297,7 +339,7 @@ def main(argv=None):
             if a.round_trip:     # in data units: the range that was applied inverts the ingest
                 row.update(round_trip(neural, ptr, dtype, strides, dims, a.ghost, used, a.repeat, coords))
             if a.error_bound is not None:
-                row.update(error_bound(neural, ptr, dtype, strides, dims, a.ghost, used, a.error_bound, a.repeat, a.packed))
+                row.update(error_bound(neural, ptr, dtype, strides, dims, a.ghost, used, a.error_bound, a.repeat, a.packed, a.resident, roi, step))
         d.free()
         for k in ("create_ms", "host_create_ms", "host_create_median_ms"):
             if k in row:

@@ -406,6 +406,64 @@ int  vnrAmdCorrectionSetResidentForm(vnrAmdCorrection, int form);
 int  vnrAmdCorrectionGetResidency(vnrAmdCorrection, vnrAmdCorrectionResidency*);
 int  vnrAmdNeuralVolumeDecodeBoxToDeviceCorrected(vnrAmdVolume neural, vnrAmdCorrection, void* d_out, const int64_t strides[3],
                                                   const int box_lo[3], const int box_size[3], void* stream, int verify_params);
+/* AMD extension: corrections to a byte budget.  CorrectionRates says what many tolerances would cost without building any of them;
+ * BuildCorrectionWithinBytes uses it to build the correction of the tightest tolerance it can find whose serialised size fits.
+ * Pointer, strides, alignment, allocation room, stream and value range are BuildCorrection's, with its refusals and messages.
+ *
+ * CorrectionRates: n_eps is 1 to 64; each eps[k] is a finite double >= 0, in any order, duplicates allowed; out: host memory, n_eps
+ * entries.  Entry k holds EXACTLY what BuildCorrection(..., eps[k], ...) followed by Serialize and SerializePacked would report on
+ * the same parameters and the same d_ref:
+ *   kind             per entry; FLOAT / DOUBLE with eps[k] == 0 is kind 2, verbatim
+ *   n_flagged        flagged cells;  n_voxels_flagged  voxels with q != 0 (kind 2: that differ)
+ *   n_groups         the sum of ceil(voxels / 64) over the flagged cells
+ *   payload_bytes    the sum over the flagged cells of pad16(voxels * width), width by the rule above on m = max |q| (kind 2: sizeof(T))
+ *   serialized_bytes         = 104 + 8 n_flagged + payload_bytes                 (the "VNRCORR1" form)
+ *   packed_payload_bytes     = pad8(n_groups) + 8 * the sum of nbits over the groups of the flagged cells
+ *   packed_serialized_bytes  = 104 + 8 n_flagged + packed_payload_bytes          (the "VNRCORP1" form)
+ *   refused          1 where some cell has m > 2^31 - 1, the case the build refuses; the entry's counts and sizes are then 0 and the
+ *                    call itself succeeds
+ * The network is evaluated once per voxel per call whatever n_eps is, chunk by chunk (VNR_AMD_DECODE_CHUNK, rounded down to whole
+ * groups of 64 codes, at least one; the result does not depend on it), in the packed form's order over all cells of the grid: one
+ * wavefront takes one group, forms r once and then, per tolerance, the build's own quantiser, two wave maxima and a ballot, folded
+ * per cell with integer atomics.  The call stores nothing in d_ref, changes no state of the volume and keeps nothing resident but
+ * the chunk scratch every round-trip call shares; its own scratch is 8 bytes per macrocell and tolerance.  Only the n_eps results
+ * cross to the host.
+ * Errors: BuildCorrection's; a null eps or out; n_eps outside 1 .. 64; an eps[k] that is negative, NaN or infinite (k and the value
+ * are named).  These four are found before the volume is looked at.
+ *
+ * BuildCorrectionWithinBytes: max_bytes bounds the serialised size in `form` (FIXED: Serialize, PACKED: SerializePacked).  The
+ * search is host code in which every step is one IEEE double operation, none contracted into an fma:
+ *   round 0:  t_j = ldexp(eps_hi, -j), j = 0 .. 15, one rate call.  eps_hi must be finite and > 0 and t_15 a normal number.  An entry
+ *       that is `refused` does not fit.  If t_0 does not fit the call returns NULL and the message names max_bytes, eps_hi and the
+ *       size at eps_hi.  J = the largest j such that every t_i, i <= J, fits; hi = t_J; J == 15 ends the search; otherwise lo = t_(J+1).
+ *   rounds 1 .. rounds (0 <= rounds <= 8):  p_i = lo + (hi - lo) * (i / 16), i = 1 .. 15, evaluated as written: one rate call of 15
+ *       tolerances.  I = the smallest i such that every p_i', i' >= I, fits.  No I: lo = p_15.  Otherwise hi = p_I, and lo = p_(I-1)
+ *       if I > 1.
+ * Then BuildCorrection(hi) runs as it always does and its result is returned.  Its size in `form` must equal the rate's figure (for
+ * PACKED this runs the device pack, which stays cached for SerializePacked); a difference is an internal error that names both.
+ * Sizes do not grow with the tolerance (rint, and floor_div of r + E by 2 E + 1, are monotone), so the search is a bisection; the
+ * prefix / suffix wording only defines the outcome without relying on that.  The integer types need no special case: their sizes
+ * depend on floor(eps) alone.
+ * report: eps = hi; bytes = its size in `form`; eps_tighter / bytes_tighter = the largest tolerance probed that did not fit and its
+ * size (0 where its entry was refused), NaN and 0 if there was none; rate_passes = the number of rate calls.  It is written on
+ * success only.
+ * Errors (NULL and a message): a null report, a form other than 0 or 1, eps_hi or rounds as above (found before the volume is looked
+ * at); those of CorrectionRates and BuildCorrection; eps_hi that does not fit. */
+typedef struct vnrAmdCorrectionRate {
+  double eps; int kind; int refused;
+  uint64_t n_flagged, n_voxels_flagged, n_groups,
+           payload_bytes, serialized_bytes,                 /* the "VNRCORR1" form */
+           packed_payload_bytes, packed_serialized_bytes;   /* the "VNRCORP1" form */
+} vnrAmdCorrectionRate;
+int vnrAmdNeuralVolumeCorrectionRates(vnrAmdVolume neural, const void* d_ref, int value_type, const int64_t strides[3],
+                                      float range_lo, float range_hi, const double* eps, int n_eps, void* stream,
+                                      vnrAmdCorrectionRate* out /* host, n_eps entries */);
+#define VNR_AMD_CORRECTION_FORM_FIXED  0
+#define VNR_AMD_CORRECTION_FORM_PACKED 1
+typedef struct vnrAmdCorrectionBudget { double eps; uint64_t bytes; double eps_tighter; uint64_t bytes_tighter; int rate_passes; } vnrAmdCorrectionBudget;
+vnrAmdCorrection vnrAmdNeuralVolumeBuildCorrectionWithinBytes(vnrAmdVolume neural, const void* d_ref, int value_type,
+    const int64_t strides[3], float range_lo, float range_hi, uint64_t max_bytes, int form, double eps_hi, int rounds,
+    void* stream, vnrAmdCorrectionBudget* report);
 /* hash-grid encode only (tcnn_impl_decoder.cu:177-230, column = level*F + f): fp16 [n][padded_width] */
 int    vnrAmdNeuralVolumeEncode(vnrAmdVolume, size_t n, const float* d_coords, uint16_t* d_features, void* stream);
 /* AMD extension: state of the brick image, the de-hashed inference copy of the hashed levels (csrc/network.h).  It is built

@@ -68,6 +68,16 @@ class CorrectionResidency(C.Structure):
                 ("index_device_bytes", C.c_uint64)]
 
 
+class CorrectionRate(C.Structure):
+    _fields_ = [("eps", C.c_double), ("kind", C.c_int), ("refused", C.c_int), ("n_flagged", C.c_uint64), ("n_voxels_flagged", C.c_uint64),
+                ("n_groups", C.c_uint64), ("payload_bytes", C.c_uint64), ("serialized_bytes", C.c_uint64), ("packed_payload_bytes", C.c_uint64),
+                ("packed_serialized_bytes", C.c_uint64)]
+
+
+class CorrectionBudget(C.Structure):
+    _fields_ = [("eps", C.c_double), ("bytes", C.c_uint64), ("eps_tighter", C.c_double), ("bytes_tighter", C.c_uint64), ("rate_passes", C.c_int)]
+
+
 def declared_symbols():
     """every function name declared in include/vnr_amd.h"""
     text = open(HEADER).read()
@@ -267,6 +277,8 @@ def lib():
     sig("vnrAmdCorrectionSetResidentForm", I, P, I)
     sig("vnrAmdCorrectionGetResidency", I, P, C.POINTER(CorrectionResidency))
     sig("vnrAmdReleaseCorrection", None, P)
+    sig("vnrAmdNeuralVolumeCorrectionRates", I, P, P, I, I64P, F, F, C.POINTER(D), I, P, C.POINTER(CorrectionRate))
+    sig("vnrAmdNeuralVolumeBuildCorrectionWithinBytes", P, P, P, I, I64P, F, F, U64, I, D, I, P, C.POINTER(CorrectionBudget))
     _lib = L
     return L
 

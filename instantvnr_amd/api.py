@@ -578,6 +578,45 @@ def vnrNeuralVolumeBuildCorrection(v, d_ref, dtype, eps, strides=None, value_ran
     return Correction(lib().vnrAmdNeuralVolumeBuildCorrection(v.h, p, t, s, lo, hi, float(eps), st))
 
 
+def vnrNeuralVolumeCorrectionRates(v, d_ref, dtype, tolerances, strides=None, value_range=None, stream=None):
+    """what vnrNeuralVolumeBuildCorrection would cost at each of 1 .. 64 `tolerances`, exactly, from one evaluation of the network and
+    without building anything (include/vnr_amd.h, "corrections to a byte budget") -> a list of dicts of vnrAmdCorrectionRate, one a
+    tolerance, in their order; `refused` as bool"""
+    p, _, t, s, _, _, st = _device_source_args(d_ref, dtype, strides, None, stream)
+    lo, hi = _round_trip_range(np.dtype(dtype), value_range)
+    try:
+        tol = [float(x) for x in np.atleast_1d(tolerances)]
+    except (TypeError, ValueError):
+        raise VnrAmdError(f"tolerances must be 1 to 64 numbers, got {tolerances!r}") from None
+    if not 1 <= len(tol) <= 64:
+        raise VnrAmdError(f"tolerances must be 1 to 64 numbers, got {len(tol)}")
+    out = (_lib.CorrectionRate * len(tol))()
+    check(lib().vnrAmdNeuralVolumeCorrectionRates(v.h, p, t, s, lo, hi, (C.c_double * len(tol))(*tol), len(tol), st, out))
+    rates = [{k: getattr(e, k) for k, _ in _lib.CorrectionRate._fields_} for e in out]
+    for r in rates:
+        r["refused"] = bool(r["refused"])
+    return rates
+
+
+CORRECTION_FORMS = {"fixed": 0, "packed": 1}
+
+
+def vnrNeuralVolumeBuildCorrectionWithinBytes(v, d_ref, dtype, max_bytes, eps_hi, form="packed", rounds=2, strides=None, value_range=None, stream=None):
+    """vnrNeuralVolumeBuildCorrection at the tightest tolerance <= eps_hi the search finds whose serialised size in `form` ("fixed":
+    to_bytes, "packed": to_packed_bytes) is at most max_bytes; `rounds` refinements after the ladder eps_hi * 2^-j.
+    -> (Correction, dict(eps, bytes, eps_tighter, bytes_tighter, rate_passes))"""
+    p, _, t, s, _, _, st = _device_source_args(d_ref, dtype, strides, None, stream)
+    lo, hi = _round_trip_range(np.dtype(dtype), value_range)
+    if form not in CORRECTION_FORMS:
+        raise VnrAmdError(f"form must be 'fixed' or 'packed', got {form!r}")
+    if int(max_bytes) < 0:
+        raise VnrAmdError(f"max_bytes must be a byte count >= 0, got {max_bytes!r}")
+    e = _lib.CorrectionBudget()
+    h = lib().vnrAmdNeuralVolumeBuildCorrectionWithinBytes(v.h, p, t, s, lo, hi, int(max_bytes), CORRECTION_FORMS[form], float(eps_hi), int(rounds), st, C.byref(e))
+    c = Correction(h)
+    return c, {k: getattr(e, k) for k, _ in _lib.CorrectionBudget._fields_}
+
+
 def vnrNeuralVolumeDecodeToDeviceCorrected(v, correction, d_ptr, strides=None, stream=None, verify_params=False, box=None):
     """vnrNeuralVolumeDecodeToDevice with `correction` applied, of the whole grid or of `box` = (lower, size) of the volume's own grid
     (`d_ptr` is then the address of the box's first voxel, `strides` None dense over the box); value type and range are the

@@ -8,6 +8,7 @@
 #include <limits>
 #include <memory>
 
+#include "correction_budget.h"
 #include "dist.h"
 #include "renderer.h"
 #include "scene.h"
@@ -600,6 +601,52 @@ vnrAmdCorrection vnrAmdNeuralVolumeBuildCorrection(vnrAmdVolume v, const void* d
 {
   return guarded_new<vnrAmdCorrection_t>([&]() {
     return new vnrAmdCorrection_t{as_neural(v)->build_correction(DeviceSource{d_ref, value_type, strides, (hipStream_t)stream}, range_lo, range_hi, eps)};
+  });
+}
+int vnrAmdNeuralVolumeCorrectionRates(vnrAmdVolume v, const void* d_ref, int value_type, const int64_t strides[3], float range_lo, float range_hi,
+                                      const double* eps, int n_eps, void* stream, vnrAmdCorrectionRate* out)
+{
+  static_assert(sizeof(vnrAmdCorrectionRate) == sizeof(CorrectionRate), "vnrAmdCorrectionRate and vnr::CorrectionRate are one layout");
+  return guarded([&]() {
+    correction_rates_check(eps, n_eps, reinterpret_cast<CorrectionRate*>(out));   // (what needs no volume comes first)
+    as_neural(v)->correction_rates(DeviceSource{d_ref, value_type, strides, (hipStream_t)stream}, range_lo, range_hi, eps, n_eps,
+                                   reinterpret_cast<CorrectionRate*>(out));
+  });
+}
+vnrAmdCorrection vnrAmdNeuralVolumeBuildCorrectionWithinBytes(vnrAmdVolume v, const void* d_ref, int value_type, const int64_t strides[3], float range_lo,
+                                                              float range_hi, uint64_t max_bytes, int form, double eps_hi, int rounds, void* stream,
+                                                              vnrAmdCorrectionBudget* report)
+{
+  return guarded_new<vnrAmdCorrection_t>([&]() {
+    if (!report) throw std::runtime_error("null result");
+    if (form != VNR_AMD_CORRECTION_FORM_FIXED && form != VNR_AMD_CORRECTION_FORM_PACKED)
+      throw std::runtime_error("unknown serialised form " + std::to_string(form) + " (0: fixed-width, 1: packed)");
+    correction_budget_check(eps_hi, rounds);
+    NeuralVolume* n = as_neural(v);
+    const DeviceSource ref{d_ref, value_type, strides, (hipStream_t)stream};
+    const bool packed = form == VNR_AMD_CORRECTION_FORM_PACKED;
+    const CorrectionBudgetResult r = correction_budget_search(
+        [&](const double* eps, int n_eps, uint64_t* bytes, int* refused) {
+          CorrectionRate rates[kCorrectionBudgetLadder];
+          n->correction_rates(ref, range_lo, range_hi, eps, n_eps, rates);
+          for (int k = 0; k < n_eps; ++k) {
+            bytes[k] = packed ? rates[k].packed_serialized_bytes : rates[k].serialized_bytes;
+            refused[k] = rates[k].refused;
+          }
+        },
+        max_bytes, eps_hi, rounds);
+    std::shared_ptr<Correction> corr = n->build_correction(ref, range_lo, range_hi, r.eps);
+    // what was promised is what was built (PACKED: the device pack, which stays cached for SerializePacked)
+    const uint64_t built = packed ? kCorrectionHeaderBytes + 8 * corr->data.cells.size() + correction_packed_payload(*corr, Runtime::get().stream).size()
+                                  : correction_serialized_bytes(corr->data);
+    if (built != r.bytes) {
+      char e[40];
+      std::snprintf(e, sizeof(e), "%.17g", r.eps);
+      throw std::runtime_error(std::string("internal error: the correction built at eps ") + e + " has " + std::to_string(built) +
+                               " serialised bytes, the rate pass gave " + std::to_string(r.bytes));
+    }
+    *report = vnrAmdCorrectionBudget{r.eps, r.bytes, r.eps_tighter, r.bytes_tighter, r.rate_passes};
+    return new vnrAmdCorrection_t{std::move(corr)};
   });
 }
 int vnrAmdCorrectionGetInfo(vnrAmdCorrection c, vnrAmdCorrectionInfo* out)

@@ -8,9 +8,14 @@
 // the flagged cells with one plain store each and reduces the error after.  The apply kernel decodes, looks the voxel's cell up and
 // stores the corrected value in the decode's 16-byte pieces.  The arithmetic is integer or single IEEE double operations
 // (include/vnr_amd.h spells it out); tests/error_bound_ref.py restates it in numpy and is matched bit for bit.
+//
+// correction_rates ("corrections to a byte budget") answers what many tolerances would cost without building any: one chunked
+// evaluation in the packed form's order, a wave per group of 64 codes, the build's quantise per tolerance, wave reductions and
+// integer atomics per cell; tests/correction_rate_ref.py restates it.  The search on top of it is correction_budget.cpp, host only.
 #include "volume.h"
 
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <limits>
 #include <type_traits>
@@ -554,6 +559,169 @@ __global__ void __launch_bounds__(kBlock) correction_apply_planes_kernel(T* __re
   for_each_chunk_voxel<T>(dst, L, b, e, op);
 }
 
+// ---- the rate pass: the sizes many tolerances would build, from one evaluation of the network ----------------------------------------------
+// (include/vnr_amd.h, "corrections to a byte budget").  The walk is the packed form's: a chunk is a run of consecutive groups of 64
+// codes over ALL cells of the grid, cell index ascending, a cell's codes in lx + cx (ly + cy lz); one wave takes one group, lane l its
+// code l, exactly as correction_pack.hip does for the flagged cells.  A group's place follows in closed form from the grid's dims: the
+// cells along an axis are 16 wide but the last, so a cell has one of 8 group counts, an x-row of cells one of 4, a z-layer one of 2.
+constexpr int kRateBatch = 16;   // tolerances a launch takes; more are further launches over the same chunk's values
+
+struct GroupWalk {
+  uint32_t dx, dy, dz, mcx, mcy, mcz;
+  uint32_t cell_groups[2][2][2];   // groups of a cell, [last in z][last in y][last in x]
+  uint64_t row_groups[2][2];       // of an x-row of cells, [last in z][last in y]
+  uint64_t layer_groups[2];        // of a z-layer of cells, [last in z]
+  uint64_t n_groups;               // of the grid
+  bool narrow;                     // every count above fits 32 bits: the divisions are 32-bit
+
+  struct Place {
+    uint32_t cell, voxels, cx, cy;   // the cell, its voxels and its extents
+    uint32_t x0, y0, z0;             // its lower corner
+    uint32_t group;                  // the group inside the cell
+  };
+  __device__ __forceinline__ Place place(uint64_t gid) const
+  {
+    uint32_t ix, iy, iz, rem;
+    if (narrow) {
+      const uint32_t g = (uint32_t)gid;
+      iz = std::min(g / (uint32_t)layer_groups[0], mcz - 1);
+      const uint32_t lz = iz == mcz - 1, in_layer = g - iz * (uint32_t)layer_groups[0];
+      iy = std::min(in_layer / (uint32_t)row_groups[lz][0], mcy - 1);
+      const uint32_t ly = iy == mcy - 1, in_row = in_layer - iy * (uint32_t)row_groups[lz][0];
+      ix = std::min(in_row / cell_groups[lz][ly][0], mcx - 1);
+      rem = in_row - ix * cell_groups[lz][ly][0];
+    } else {
+      iz = (uint32_t)std::min<uint64_t>(gid / layer_groups[0], mcz - 1);
+      const uint32_t lz = iz == mcz - 1;
+      const uint64_t in_layer = gid - iz * layer_groups[0];
+      iy = (uint32_t)std::min<uint64_t>(in_layer / row_groups[lz][0], mcy - 1);
+      const uint32_t ly = iy == mcy - 1;
+      const uint64_t in_row = in_layer - iy * row_groups[lz][0];
+      ix = (uint32_t)std::min<uint64_t>(in_row / cell_groups[lz][ly][0], mcx - 1);
+      rem = (uint32_t)(in_row - (uint64_t)ix * cell_groups[lz][ly][0]);
+    }
+    Place p;
+    p.x0 = ix * 16u; p.y0 = iy * 16u; p.z0 = iz * 16u;
+    p.cx = std::min(16u, dx - p.x0); p.cy = std::min(16u, dy - p.y0);
+    p.voxels = p.cx * p.cy * std::min(16u, dz - p.z0);
+    p.cell = ix + mcx * (iy + mcy * iz);
+    p.group = rem;
+    return p;
+  }
+};
+
+// the voxel centres of the groups [g0, g0 + n / 64) in that order: decode_coords_kernel's arithmetic.  A lane beyond its cell's voxels
+// (the last group of a ragged cell) gets the cell's last voxel: its value is evaluated and never read.
+__global__ void __launch_bounds__(kBlock) correction_rate_coords_kernel(GroupWalk w, uint64_t g0, uint32_t n, vec3f rdims, float* __restrict__ coords)
+{
+  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= n) return;
+  const GroupWalk::Place p = w.place(g0 + (t >> 6));
+  const uint32_t li = std::min(p.group * 64u + (t & 63u), p.voxels - 1u);
+  const uint32_t row = li / p.cx, lx = li - row * p.cx, lz = row / p.cy, ly = row - lz * p.cy;
+  coords[3 * (size_t)t + 0] = ((float)(int)(p.x0 + lx) + 0.5f) * rdims.x;
+  coords[3 * (size_t)t + 1] = ((float)(int)(p.y0 + ly) + 0.5f) * rdims.y;
+  coords[3 * (size_t)t + 2] = ((float)(int)(p.z0 + lz) + 0.5f) * rdims.z;
+}
+
+struct RateBatch {
+  Quantiser k[kRateBatch];
+  int n;
+};
+struct RateCell { uint32_t max_q, nbits; };   // per (tolerance, macrocell): max |q| saturated, the sum of its groups' nbits
+
+__device__ __forceinline__ uint32_t wave_max(uint32_t v)
+{
+  for (int off = 32; off > 0; off >>= 1) v = std::max(v, (uint32_t)__shfl_xor(v, off, 64));
+  return v;
+}
+
+// groups [g0, g0 + n_groups) of the walk, their values in values[64 * (group - g0) + lane].  A lane reads its voxel of ref through the
+// strides, converts its value and forms the code of every tolerance of the batch with the build's quantise; per tolerance the wave
+// reduces max |q| and the bit length of the largest z (the group's nbits) and counts the codes != 0 with a ballot.  Lane 0 folds the
+// two maxima into the cell's pair (a cell has up to 64 groups, which may lie in several blocks and chunks) and the count into the
+// block's; all three are integers, so the result is exact whatever the order.  stats[j * n_cells + cell], nonzero[j]: of tolerance j.
+template <typename T>
+__global__ void __launch_bounds__(kBlock) correction_rate_kernel(const T* __restrict__ ref, int64_t sx, int64_t sy, int64_t sz, GroupWalk w, uint64_t g0, uint32_t n_groups,
+                                                                 const float* __restrict__ values, Conversion c, RateBatch batch, uint64_t n_cells,
+                                                                 RateCell* __restrict__ stats, unsigned long long* __restrict__ nonzero)
+{
+  __shared__ uint32_t block_nonzero[kRateBatch];   // (a chunk holds at most 2^28 samples)
+  if (threadIdx.x < kRateBatch) block_nonzero[threadIdx.x] = 0;
+  __syncthreads();
+  const uint32_t lane = threadIdx.x & 63u, waves = kBlock / 64;
+  for (uint32_t g = blockIdx.x * waves + (threadIdx.x >> 6); g < n_groups; g += gridDim.x * waves) {
+    const GroupWalk::Place p = w.place(g0 + g);
+    const uint32_t li = p.group * 64u + lane;
+    const bool has = li < p.voxels;   // the pack fills the other lanes with codes of value 0
+    T rv = T(0), dec = T(0);
+    if (has) {
+      const uint32_t row = li / p.cx, lx = li - row * p.cx, lz = row / p.cy, ly = row - lz * p.cy;
+      rv = ref[(int64_t)(p.x0 + lx) * sx + (int64_t)(p.y0 + ly) * sy + (int64_t)(p.z0 + lz) * sz];
+      dec = convert_value<T>(values[(size_t)g * 64 + lane], c);
+    }
+    for (int j = 0; j < batch.n; ++j) {
+      const Quantiser& k = batch.k[j];
+      int64_t q = 0; uint32_t aq = 0; bool nan;
+      uint64_t z = 0;
+      if (has) {
+        quantise<T>(dec, rv, k, q, aq, nan);
+        if constexpr (std::is_floating_point_v<T>) z = k.kind == kCorrectionVerbatim ? (uint64_t)bits_of(rv) : ((uint64_t)q << 1) ^ (uint64_t)(q >> 63);
+        else z = ((uint64_t)q << 1) ^ (uint64_t)(q >> 63);
+      }
+      const uint64_t differ = __ballot(q != 0);
+      if (differ == 0 && k.kind != kCorrectionVerbatim) continue;   // a group of zeros: nothing to fold (verbatim: its planes are ref's bits)
+      const uint32_t m = wave_max(aq), nbits = wave_max(z ? 64u - (uint32_t)__clzll((long long)z) : 0u);
+      if (lane == 0) {
+        RateCell* s = stats + ((uint64_t)j * n_cells + p.cell);
+        if (m) atomicMax(&s->max_q, m);
+        if (nbits) atomicAdd(&s->nbits, nbits);
+        if (differ) atomicAdd(&block_nonzero[j], (uint32_t)__popcll(differ));
+      }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < (uint32_t)batch.n && block_nonzero[threadIdx.x]) atomicAdd(nonzero + threadIdx.x, (unsigned long long)block_nonzero[threadIdx.x]);
+}
+
+struct RateSums { uint64_t n_flagged, n_groups, payload_bytes, sum_nbits, n_voxels_flagged, refused; };
+struct RateWidths { uint8_t verbatim[64]; };   // per tolerance: sizeof(T) for kind 2, 0 for the width rule on max |q|
+
+__device__ __forceinline__ uint64_t block_sum(uint64_t v)
+{
+  for (int off = 32; off > 0; off >>= 1) v += (uint64_t)__shfl_down((unsigned long long)v, off, 64);
+  __shared__ uint64_t w_sum[kBlock / 64];
+  if ((threadIdx.x & 63) == 0) w_sum[threadIdx.x >> 6] = v;
+  __syncthreads();
+  uint64_t r = 0;
+  for (int i = 0; i < kBlock / 64; ++i) r += w_sum[i];
+  __syncthreads();
+  return r;
+}
+
+// block j: the per-cell pairs of tolerance j -> its sums, with the header's width rule and the paddings of both serialised forms
+__global__ void __launch_bounds__(kBlock) correction_rate_final_kernel(const RateCell* __restrict__ stats, uint64_t n_cells, CellGrid g, RateWidths widths,
+                                                                       const unsigned long long* __restrict__ nonzero, RateSums* __restrict__ out)
+{
+  const uint32_t j = blockIdx.x;
+  const uint32_t verbatim = widths.verbatim[j];
+  uint64_t n_flagged = 0, n_groups = 0, payload = 0, nbits = 0, refused = 0;
+  for (uint64_t cl = threadIdx.x; cl < n_cells; cl += kBlock) {
+    const RateCell s = stats[(uint64_t)j * n_cells + cl];
+    if (s.max_q == 0) continue;
+    if (s.max_q > 0x7fffffffu) refused = 1;
+    const uint32_t ix = (uint32_t)(cl % g.mcx), iy = (uint32_t)(cl / g.mcx % g.mcy), iz = (uint32_t)(cl / ((uint64_t)g.mcx * g.mcy));
+    const uint64_t voxels = (uint64_t)std::min(16u, g.dx - 16u * ix) * std::min(16u, g.dy - 16u * iy) * std::min(16u, g.dz - 16u * iz);
+    const uint32_t width = verbatim ? verbatim : (s.max_q <= 127u ? 1u : (s.max_q <= 32767u ? 2u : 4u));
+    ++n_flagged;
+    n_groups += (voxels + 63) / 64;
+    payload += (voxels * width + 15) / 16 * 16;
+    nbits += s.nbits;
+  }
+  n_flagged = block_sum(n_flagged); n_groups = block_sum(n_groups); payload = block_sum(payload); nbits = block_sum(nbits); refused = block_sum(refused);
+  if (threadIdx.x == 0) out[j] = RateSums{n_flagged, n_groups, payload, nbits, nonzero[j], refused};
+}
+
 // ---- host side: decode.hip's dispatch, validation and chunking ------------------------------------------------------------------------------
 template <typename F>
 void dispatch_type(int type, F&& f)
@@ -832,6 +1000,124 @@ std::shared_ptr<Correction> NeuralVolume::build_correction(const DeviceSource& r
     index_to_voxel(after.worst, L, corr->worst_after);
   }
   return corr;
+}
+
+namespace {
+
+GroupWalk make_group_walk(vec3i d)
+{
+  GroupWalk w{};
+  w.dx = (uint32_t)d.x; w.dy = (uint32_t)d.y; w.dz = (uint32_t)d.z;
+  w.mcx = (w.dx + 15) / 16; w.mcy = (w.dy + 15) / 16; w.mcz = (w.dz + 15) / 16;
+  const uint32_t ex[2] = {16, w.dx - 16 * (w.mcx - 1)}, ey[2] = {16, w.dy - 16 * (w.mcy - 1)}, ez[2] = {16, w.dz - 16 * (w.mcz - 1)};
+  for (int z = 0; z < 2; ++z) {
+    for (int y = 0; y < 2; ++y) {
+      for (int x = 0; x < 2; ++x) w.cell_groups[z][y][x] = (ex[x] * ey[y] * ez[z] + 63) / 64;
+      w.row_groups[z][y] = (uint64_t)(w.mcx - 1) * w.cell_groups[z][y][0] + w.cell_groups[z][y][1];
+    }
+    w.layer_groups[z] = (uint64_t)(w.mcy - 1) * w.row_groups[z][0] + w.row_groups[z][1];
+  }
+  w.n_groups = (uint64_t)(w.mcz - 1) * w.layer_groups[0] + w.layer_groups[1];
+  w.narrow = std::max({w.n_groups, w.layer_groups[0], w.row_groups[0][0], w.row_groups[1][0]}) <= 0xffffffffull;
+  return w;
+}
+
+std::string str_g(double v)
+{
+  char b[40];
+  std::snprintf(b, sizeof(b), "%.17g", v);
+  return b;
+}
+
+}  // namespace
+
+void NeuralVolume::correction_rates(const DeviceSource& ref, float range_lo, float range_hi, const double* eps, int n_eps, CorrectionRate* out)
+{
+  if (!net_.valid()) throw std::runtime_error("neural volume has no valid network");
+  correction_rates_check(eps, n_eps, out);
+  const vec3i grid = desc.dims;
+  vec3i lower;
+  const BoxLayout L = validate_box_array(ref.data, ref.type, ref.strides, nullptr, nullptr, grid, lower, range_lo, range_hi);
+  const int64_t sx = ref.strides ? ref.strides[0] : 1, sy = ref.strides ? ref.strides[1] : (int64_t)L.bx, sz = ref.strides ? ref.strides[2] : (int64_t)(L.bx * L.by);
+  const vec3f rdims = {1.0f / (float)grid.x, 1.0f / (float)grid.y, 1.0f / (float)grid.z};
+  const Conversion c{range_lo, range_hi - range_lo, range_lo < range_hi};
+  const bool is_float = correction_type_is_float(ref.type);
+  const uint32_t ts = (uint32_t)device_value_type_size(ref.type);
+  const CellGrid g = make_cell_grid(grid);
+  const GroupWalk w = make_group_walk(grid);
+  const int dims[3] = {grid.x, grid.y, grid.z};
+  const uint64_t n_cells = correction_n_cells(dims);
+  // a chunk: whole groups, as many as VNR_AMD_DECODE_CHUNK samples hold (at least one)
+  const uint64_t chunk_groups = std::min(std::max<uint64_t>(1, chunk_samples() / 64), w.n_groups);
+
+  std::vector<Quantiser> quantisers(n_eps);
+  RateWidths widths{};
+  for (int j = 0; j < n_eps; ++j) {
+    const uint32_t kind = !is_float ? kCorrectionInteger : (eps[j] > 0.0 ? kCorrectionFloat : kCorrectionVerbatim);
+    quantisers[j] = make_quantiser(kind, eps[j]);
+    widths.verbatim[j] = kind == kCorrectionVerbatim ? (uint8_t)ts : (uint8_t)0;
+  }
+
+  dd_coords_.ensure(3 * 64 * chunk_groups);
+  dd_values_.ensure(64 * chunk_groups);
+  DeviceBuffer<RateCell> stats(MemTag::Network);
+  DeviceBuffer<unsigned long long> nonzero(MemTag::Network);
+  DeviceBuffer<RateSums> sums(MemTag::Network);
+  stats.resize(n_cells * (uint64_t)n_eps);
+  nonzero.resize(n_eps);
+  sums.resize(n_eps);
+  EventGuard ev;
+  wait_for(ref.producer, stream, ev);
+  stats.zero(stream);
+  nonzero.zero(stream);
+  const uint32_t max_blocks = (uint32_t)Runtime::get().n_cus * 8;
+  for (uint64_t g0 = 0; g0 < w.n_groups; g0 += chunk_groups) {
+    const uint32_t n_groups = (uint32_t)std::min(chunk_groups, w.n_groups - g0), n = 64 * n_groups;
+    correction_rate_coords_kernel<<<div_round_up(n, kBlock), kBlock, 0, stream>>>(w, g0, n, rdims, dd_coords_.ptr);
+    VNR_HIP_CHECK(hipGetLastError());
+    net_.inference(dd_coords_.ptr, dd_values_.ptr, n, nullptr, n, stream);   // the one evaluation of these voxels, whatever n_eps is
+    const uint32_t blocks = std::max(1u, std::min(div_round_up(n_groups, kBlock / 64), max_blocks));
+    for (int j0 = 0; j0 < n_eps; j0 += kRateBatch) {
+      RateBatch batch{};
+      batch.n = std::min(kRateBatch, n_eps - j0);
+      for (int j = 0; j < batch.n; ++j) batch.k[j] = quantisers[j0 + j];
+      dispatch_type(ref.type, [&](auto* tag) {
+        using T = std::remove_pointer_t<decltype(tag)>;
+        correction_rate_kernel<T><<<blocks, kBlock, 0, stream>>>((const T*)ref.data, sx, sy, sz, w, g0, n_groups, dd_values_.ptr, c, batch, n_cells,
+                                                                 stats.ptr + (uint64_t)j0 * n_cells, nonzero.ptr + j0);
+      });
+      VNR_HIP_CHECK(hipGetLastError());
+    }
+  }
+  correction_rate_final_kernel<<<n_eps, kBlock, 0, stream>>>(stats.ptr, n_cells, g, widths, nonzero.ptr, sums.ptr);
+  VNR_HIP_CHECK(hipGetLastError());
+  std::vector<RateSums> host(n_eps);
+  sums.download(host.data(), n_eps, stream);   // (synchronises)
+  for (int j = 0; j < n_eps; ++j) {
+    const RateSums& s = host[j];
+    CorrectionRate r{};
+    r.eps = eps[j];
+    r.kind = (int)quantisers[j].kind;
+    r.refused = s.refused ? 1 : 0;
+    if (!r.refused) {
+      r.n_flagged = s.n_flagged; r.n_voxels_flagged = s.n_voxels_flagged; r.n_groups = s.n_groups;
+      r.payload_bytes = s.payload_bytes;
+      r.serialized_bytes = kCorrectionHeaderBytes + 8 * s.n_flagged + s.payload_bytes;
+      r.packed_payload_bytes = correction_group_table_bytes(s.n_groups) + 8 * s.sum_nbits;
+      r.packed_serialized_bytes = kCorrectionHeaderBytes + 8 * s.n_flagged + r.packed_payload_bytes;
+    }
+    out[j] = r;
+  }
+}
+
+void correction_rates_check(const double* eps, int n_eps, const CorrectionRate* out)
+{
+  if (!eps) throw std::runtime_error("null eps: the tolerances are missing");
+  if (!out) throw std::runtime_error("null result");
+  if (n_eps < 1 || n_eps > kCorrectionMaxRates) throw std::runtime_error("n_eps must be 1 .. 64, got " + std::to_string(n_eps));
+  for (int k = 0; k < n_eps; ++k)
+    if (!(eps[k] >= 0.0) || !std::isfinite(eps[k]))
+      throw std::runtime_error("eps[" + std::to_string(k) + "] must be a finite tolerance >= 0 in data units, got " + str_g(eps[k]));
 }
 
 void correction_make_resident(Correction& corr, hipStream_t stream)

@@ -156,6 +156,17 @@ void correction_make_resident(Correction& corr, hipStream_t stream);
 // vnrAmdCorrectionSetResidentForm: a correction that holds nothing on the device only notes the form, any other is converted at once
 void correction_set_resident_form(Correction& corr, int form, hipStream_t stream);
 
+// vnrAmdCorrectionRate (include/vnr_amd.h, "corrections to a byte budget"), field for field: what build_correction at eps followed by
+// both serialisations would report
+struct CorrectionRate {
+  double eps;
+  int kind, refused;
+  uint64_t n_flagged, n_voxels_flagged, n_groups, payload_bytes, serialized_bytes, packed_payload_bytes, packed_serialized_bytes;
+};
+constexpr int kCorrectionMaxRates = 64;
+// what a rate call refuses before it looks at the volume: a null eps or out, n_eps outside 1 .. 64, an eps[k] that is negative, NaN or infinite
+void correction_rates_check(const double* eps, int n_eps, const CorrectionRate* out);
+
 struct VolumeDesc {  // MultiVolume, instantvnr_types.h:40-56 (single timestep)
   vec3i dims{0, 0, 0};
   int type = 8;  // VALUE_TYPE_FLOAT
@@ -311,6 +322,10 @@ public:
   // voxels are evaluated.  verify_params: refuse unless the parameters hash to what the correction was built on.
   std::shared_ptr<Correction> build_correction(const DeviceSource& ref, float range_lo, float range_hi, double eps);
   void decode_to_device_corrected(Correction& corr, const DeviceTarget& out, const int box_lo[3], const int box_size[3], bool verify_params);
+  // correction_rates: for each of n_eps (1 .. 64) tolerances exactly the counts and the sizes in both serialised forms that
+  // build_correction(ref, range, eps[k]) would give, from ONE chunked evaluation of the network; nothing is built, `ref` is only read,
+  // and only the n_eps results cross to the host (out: host memory).
+  void correction_rates(const DeviceSource& ref, float range_lo, float range_hi, const double* eps, int n_eps, CorrectionRate* out);
   uint64_t params_hash();   // FNV-1a 64 of the fp16 parameter blob
   // network.cu:328-365 / :367-405: raw fp32, z-slice by z-slice, every slice padded to a multiple of 256 values
   void save_inference_volume(const std::string& filename);

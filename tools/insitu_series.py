@@ -35,6 +35,14 @@ ingest time are printed.
                          (vnrAmdNeuralVolumeDecodeBoxToDeviceCorrected), check it on the host against the step's own array (every
                          voxel within max_abs_after) and against the same box cut out of the whole-grid corrected decode (equal
                          bytes), and time it beside the plain vnrAmdNeuralVolumeDecodeToDevice of the box
+  --byte-budget BYTES    after each step's training: the correction of the tightest tolerance the search finds whose serialised
+                         size is at most BYTES (vnrAmdNeuralVolumeBuildCorrectionWithinBytes).  eps_hi is the step's max_abs from
+                         the error report (vnrAmdNeuralVolumeErrorAgainstDevice), at which nothing is flagged.  Per step: the chosen
+                         eps and its bytes, the tolerance just below that did not fit and its bytes, the compressed bytes (params.json
+                         plus the correction) and the ratio, max_abs_after, the rate passes; the whole call timed, beside one rate call
+                         of 16 tolerances (vnrAmdNeuralVolumeCorrectionRates)
+  --budget-form FORM     with --byte-budget: fixed | packed, the serialised form BYTES bounds                     [packed]
+  --budget-rounds N      with --byte-budget: refinement rounds after the ladder eps_hi * 2^-j, 0 .. 8             [2]
   --guided               error-guided batches instead of the series (vnrAmdNeuralVolumeGuideSamplingByError): ONE static field, the
                          synthetic blob field with plateaus at both ends, trained --steps-per-frame steps in all, twice with the same
                          seeds: once with the error map re-installed as sampling weights every --refresh-every steps, once with
@@ -69,7 +77,12 @@ clock).  The kernels are correction_pack_measure_kernel, correction_pack_planes_
 that reads the planes (correction_apply_planes_kernel); no unpack.
 
 The --roi times are host clocks around whole calls as well, each warmed up once: "roi_apply" evaluates the network for the box's
-voxels alone and applies the correction in the resident form, "roi_plain_decode" is DecodeToDevice of the same box."""
+voxels alone and applies the correction in the resident form, "roi_plain_decode" is DecodeToDevice of the same box.
+
+The --byte-budget times are host clocks around whole calls, each warmed up once: "budget_ms" is the whole
+vnrAmdNeuralVolumeBuildCorrectionWithinBytes (1 + rounds rate passes at most, one build, for the packed form the device pack),
+"rate_pass_ms" one vnrAmdNeuralVolumeCorrectionRates call over the ladder's 16 tolerances: one evaluation of the network.  The
+kernels are correction_rate_coords_kernel, correction_rate_kernel and correction_rate_final_kernel."""
 import argparse
 import json
 import os
@@ -206,6 +219,39 @@ def error_bound(neural, ptr, dtype, strides, dims, ghost, value_range, eps, repe
     return row
 
 
+def byte_budget(neural, ptr, dtype, strides, dims, value_range, max_bytes, form, rounds, repeat):
+    """-> the --byte-budget columns of one step.  `ptr` is the step's own device array (the reference of the correction)."""
+    eps_hi = api.vnrNeuralVolumeErrorAgainstDevice(neural, ptr, dtype, strides, None, value_range)["max_abs"]
+    raw = dims[0] * dims[1] * dims[2] * dtype.itemsize
+    n_params = len(api.vnrNeuralVolumeSerializeParams(neural))
+    row = {"byte_budget": max_bytes, "budget_form": form, "budget_rounds": rounds, "eps_hi": eps_hi, "raw_bytes": raw, "params_bytes": n_params}
+    if not eps_hi > 0:      # the decode is exact already: there is no ladder below 0
+        return row
+    held = []
+
+    def build():
+        c, rep = api.vnrNeuralVolumeBuildCorrectionWithinBytes(neural, ptr, dtype, max_bytes, eps_hi, form, rounds, strides, value_range)
+        held.append(c)
+        while len(held) > 1:
+            held.pop(0).release()
+        return c, rep
+    try:
+        (corr, rep), best, median = timed(build, repeat, 1)
+    except api.VnrAmdError as e:      # not even eps_hi fits
+        row["budget_refused"] = str(e)
+        return row
+    blob = corr.to_packed_bytes() if form == "packed" else corr.to_bytes()
+    row.update(budget_eps=rep["eps"], budget_bytes=rep["bytes"], serialized_equals_report=len(blob) == rep["bytes"], eps_tighter=rep["eps_tighter"],
+               bytes_tighter=rep["bytes_tighter"], rate_passes=rep["rate_passes"], compressed_bytes=n_params + rep["bytes"],
+               ratio=round(raw / (n_params + rep["bytes"]), 3), max_abs_after=corr.info()["max_abs_after"], budget_ms=round(best, 4),
+               budget_median_ms=round(median, 4))
+    corr.release()
+    ladder = [eps_hi * 2.0 ** -j for j in range(16)]
+    _, best, median = timed(lambda: api.vnrNeuralVolumeCorrectionRates(neural, ptr, dtype, ladder, strides, value_range), repeat, 1)
+    row.update(rate_pass_ms=round(best, 4), rate_pass_median_ms=round(median, 4))
+    return row
+
+
 def guided(a):
     """the --guided run: the same field, model and seeds trained with error-guided and with uniform batches, side by side"""
     dims = (a.size,) * 3
@@ -264,6 +310,9 @@ def main(argv=None):
     p.add_argument("--packed", action="store_true")
     p.add_argument("--resident", default="fixed", choices=["fixed", "packed"])
     p.add_argument("--roi", default=None, metavar="x0,y0,z0,sx,sy,sz")
+    p.add_argument("--byte-budget", type=int, default=None, metavar="BYTES")
+    p.add_argument("--budget-form", default="packed", choices=["fixed", "packed"])
+    p.add_argument("--budget-rounds", type=int, default=2, metavar="N")
     p.add_argument("--guided", action="store_true")
     p.add_argument("--uniform-fraction", type=float, default=0.25)
     p.add_argument("--refresh-every", type=int, default=100)
@@ -277,6 +326,8 @@ def main(argv=None):
         p.error("--error-bound needs a trained network (--steps-per-frame > 0) and a finite EPS >= 0")
     if a.packed and a.error_bound is None:
         p.error("--packed needs --error-bound EPS")
+    if a.byte_budget is not None and (not a.steps_per_frame or a.byte_budget < 0 or not 0 <= a.budget_rounds <= 8):
+        p.error("--byte-budget needs a trained network (--steps-per-frame > 0), BYTES >= 0 and --budget-rounds 0 .. 8")
     roi = None
     if a.roi is not None or a.resident != "fixed":
         if a.error_bound is None:
@@ -340,6 +391,8 @@ def main(argv=None):
                 row.update(round_trip(neural, ptr, dtype, strides, dims, a.ghost, used, a.repeat, coords))
             if a.error_bound is not None:
                 row.update(error_bound(neural, ptr, dtype, strides, dims, a.ghost, used, a.error_bound, a.repeat, a.packed, a.resident, roi, step))
+            if a.byte_budget is not None:
+                row.update(byte_budget(neural, ptr, dtype, strides, dims, used, a.byte_budget, a.budget_form, a.budget_rounds, a.repeat))
         d.free()
         for k in ("create_ms", "host_create_ms", "host_create_median_ms"):
             if k in row:

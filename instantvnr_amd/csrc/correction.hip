@@ -2,102 +2,23 @@
 // decode with a correction applied.  The last step of the in-situ loop of ingest.hip / decode.hip / guided_sampler.hip.
 //
 // build_correction walks the whole grid twice in chunks of linear voxel indices, exactly as decode.hip's error report does (the same
-// VNR_AMD_DECODE_CHUNK, scratch and decode_chunk; the walker, the conversion and the validation below are copies of decode.hip's,
-// which keeps its own): pass 1 reduces max |q| per macrocell (one atomicMax per cell change of a lane) and the error before; the host
-// turns the cell map into per-cell {payload offset, code width}; pass 2 evaluates the network again, stores every voxel's code of
-// the flagged cells with one plain store each and reduces the error after.  The apply kernel decodes, looks the voxel's cell up and
-// stores the corrected value in the decode's 16-byte pieces.  The arithmetic is integer or single IEEE double operations
-// (include/vnr_amd.h spells it out); tests/error_bound_ref.py restates it in numpy and is matched bit for bit.
+// VNR_AMD_DECODE_CHUNK, scratch and decode_chunk; the walker, the conversion, the validation and the worst-voxel reduction are
+// box_walk.h's, the very ones decode.hip uses): pass 1 reduces max |q| per macrocell (one atomicMax per cell change of a lane) and
+// the error before; the host turns the cell map into per-cell {payload offset, code width}; pass 2 evaluates the network again,
+// stores every voxel's code of the flagged cells with one plain store each and reduces the error after.  The apply kernel decodes,
+// looks the voxel's cell up and stores the corrected value in the decode's 16-byte pieces.  The arithmetic is integer or single IEEE
+// double operations (include/vnr_amd.h spells it out); tests/error_bound_ref.py restates it in numpy and is matched bit for bit.
 //
 // correction_rates ("corrections to a byte budget") answers what many tolerances would cost without building any: one chunked
 // evaluation in the packed form's order, a wave per group of 64 codes, the build's quantise per tolerance, wave reductions and
 // integer atomics per cell; tests/correction_rate_ref.py restates it.  The search on top of it is correction_budget.cpp, host only.
-#include "volume.h"
+#include "box_walk.h"
 
-#include <algorithm>
 #include <cstdio>
-#include <cstdlib>
-#include <limits>
-#include <type_traits>
 
 namespace vnr {
 
 namespace {
-
-constexpr int kBlock = 256;
-constexpr uint64_t kDefaultChunk = 1ull << 22, kMaxChunk = 1ull << 28;   // decode.hip's
-
-// ---- decode.hip's walk of the caller's array ---------------------------------------------------------------------------------------------
-// runs of run_len contiguous elements; run r starts at element (r % runs_y) * sy + (r / runs_y) * sz and holds the box's linear indices
-// [r * run_len, (r + 1) * run_len).  sx != 1: no runs, one voxel at a time.
-struct BoxLayout {
-  uint64_t bx, by, bz;
-  int64_t sx, sy, sz;
-  uint64_t run_len, runs_y;
-  bool gather;
-};
-
-template <typename T> struct PieceOf { static constexpr int n = 16 / (int)sizeof(T); };
-
-// For the linear box indices [b, e): f.piece(T* p, i) for every whole 16-byte piece (p 16-byte aligned, N voxels from index i on)
-// and f.one(T* p, i) for every other voxel.  T is const-qualified for a source.
-template <typename T, typename F>
-__device__ __forceinline__ void for_each_chunk_voxel(T* base, const BoxLayout& L, uint64_t b, uint64_t e, F& f)
-{
-  constexpr int N = PieceOf<std::remove_const_t<T>>::n;
-  if (L.gather) {
-    for (uint64_t i = b + (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < e; i += (uint64_t)gridDim.x * kBlock) {
-      const uint64_t x = i % L.bx, yz = i / L.bx, y = yz % L.by, z = yz / L.by;
-      f.one(base + ((int64_t)x * L.sx + (int64_t)y * L.sy + (int64_t)z * L.sz), i);
-    }
-    return;
-  }
-  const uint64_t r0 = b / L.run_len, r1 = (e - 1) / L.run_len;   // the runs this chunk touches
-  // per run: 1 (the head) + the 16-byte pieces that cover the longest part a run can have inside this chunk
-  const uint64_t P = 1 + (std::min(L.run_len, e - b) + N - 1) / N, work = (r1 - r0 + 1) * P;
-  for (uint64_t g = (uint64_t)blockIdx.x * kBlock + threadIdx.x; g < work; g += (uint64_t)gridDim.x * kBlock) {
-    uint64_t r, p;
-    if (work <= 0xffffffffull) { const uint32_t q = (uint32_t)g / (uint32_t)P; r = r0 + q; p = (uint32_t)g - q * (uint32_t)P; }
-    else { const uint64_t q = g / P; r = r0 + q; p = g - q * P; }
-    const uint64_t run_first = r * L.run_len;
-    const uint64_t lo = std::max(b, run_first), hi = std::min(e, run_first + L.run_len);   // the run's part inside the chunk
-    const uint64_t len = hi - lo;
-    uint64_t ry, rz;
-    if (r <= 0xffffffffull) { rz = (uint32_t)r / (uint32_t)L.runs_y; ry = (uint32_t)r - (uint32_t)rz * (uint32_t)L.runs_y; }
-    else { rz = r / L.runs_y; ry = r - rz * L.runs_y; }
-    T* part = base + ((int64_t)ry * L.sy + (int64_t)rz * L.sz + (int64_t)(lo - run_first));
-    // elements in front of the first 16-byte boundary of this part (the array is aligned to its element size)
-    const uint64_t head = std::min<uint64_t>(((16u - (uint32_t)((uintptr_t)part & 15u)) & 15u) / (uint32_t)sizeof(T), len);
-    if (p == 0) {
-      for (uint64_t k = 0; k < head; ++k) f.one(part + k, lo + k);
-      continue;
-    }
-    const uint64_t e0 = head + (p - 1) * N;
-    if (e0 >= len) continue;
-    if (e0 + N <= len) f.piece(part + e0, lo + e0);
-    else for (uint64_t k = e0; k < len; ++k) f.one(part + k, lo + k);
-  }
-}
-
-// ---- decode.hip's conversion: network output -> the typed voxel ------------------------------------------------------------------------
-struct Conversion {
-  float lo, width;   // d = v * width + lo, two roundings
-  bool scale;        // false: d = v
-};
-
-template <typename T>
-__device__ __forceinline__ T convert_value(float v, const Conversion& c)
-{
-  const float d = c.scale ? __fadd_rn(__fmul_rn(v, c.width), c.lo) : v;
-  if constexpr (std::is_same_v<T, float>) return d;
-  else if constexpr (std::is_same_v<T, double>) return (double)d;
-  else {
-    const double r = rint((double)d);   // ties to even
-    constexpr double tmin = (double)std::numeric_limits<T>::lowest(), tmax = (double)std::numeric_limits<T>::max();
-    if (r != r) return (T)0;
-    return r <= tmin ? std::numeric_limits<T>::lowest() : (r >= tmax ? std::numeric_limits<T>::max() : (T)r);
-  }
-}
 
 // ---- the quantiser (include/vnr_amd.h, "error-bounded round trip") ----------------------------------------------------------------------
 struct Quantiser {
@@ -166,70 +87,7 @@ struct CellGrid {
   }
 };
 
-__device__ __forceinline__ void split_index(uint64_t i, uint64_t bx, uint64_t by, uint32_t& x, uint32_t& y, uint32_t& z)
-{
-  const uint64_t yz = i / bx;
-  x = (uint32_t)(i - yz * bx); y = (uint32_t)(yz % by); z = (uint32_t)(yz / by);
-}
-
-template <typename T> struct alignas(16) Piece { T v[PieceOf<T>::n]; };
-
-// ---- reductions ---------------------------------------------------------------------------------------------------------------------------
-struct Partial {
-  double max_abs;      // -1: no voxel yet
-  uint64_t worst;      // the lowest linear index among equals
-  uint64_t n_a, n_b;   // pass 1: voxels over the tolerance, NaN voxels
-};
-
-__device__ __forceinline__ void block_reduce(double& mx, uint64_t& mi, uint64_t& na, uint64_t& nb)
-{
-  for (int off = 32; off > 0; off >>= 1) {
-    const double omx = __shfl_down(mx, off, 64);
-    const uint64_t omi = (uint64_t)__shfl_down((unsigned long long)mi, off, 64);
-    na += (uint64_t)__shfl_down((unsigned long long)na, off, 64);
-    nb += (uint64_t)__shfl_down((unsigned long long)nb, off, 64);
-    if (omx > mx || (omx == mx && omi < mi)) { mx = omx; mi = omi; }
-  }
-  __shared__ double w_mx[kBlock / 64];
-  __shared__ uint64_t w_mi[kBlock / 64], w_na[kBlock / 64], w_nb[kBlock / 64];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) { w_mx[wave] = mx; w_mi[wave] = mi; w_na[wave] = na; w_nb[wave] = nb; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kBlock / 64; ++w) {
-      if (w_mx[w] > mx || (w_mx[w] == mx && w_mi[w] < mi)) { mx = w_mx[w]; mi = w_mi[w]; }
-      na += w_na[w]; nb += w_nb[w];
-    }
-  }
-}
-
-__global__ void __launch_bounds__(kBlock) correction_init_kernel(Partial* __restrict__ partials, uint32_t n)
-{
-  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-  if (i < n) partials[i] = Partial{-1.0, ~0ull, 0, 0};
-}
-
-__global__ void __launch_bounds__(kBlock) correction_final_kernel(const Partial* __restrict__ partials, uint32_t n, Partial* __restrict__ out)
-{
-  double mx = -1.0;
-  uint64_t mi = ~0ull, na = 0, nb = 0;
-  for (uint32_t i = threadIdx.x; i < n; i += kBlock) {
-    const Partial p = partials[i];
-    if (p.max_abs > mx || (p.max_abs == mx && p.worst < mi)) { mx = p.max_abs; mi = p.worst; }
-    na += p.n_a; nb += p.n_b;
-  }
-  block_reduce(mx, mi, na, nb);
-  if (threadIdx.x == 0) *out = Partial{mx, mi, na, nb};
-}
-
-__device__ __forceinline__ void merge_partial(Partial* __restrict__ partials, double mx, uint64_t mi, uint64_t na, uint64_t nb)
-{
-  // one partial per block; the launches of one pass run one behind the other on one stream, so block k owns partials[k] throughout
-  Partial p = partials[blockIdx.x];
-  if (mx > p.max_abs || (mx == p.max_abs && mi < p.worst)) { p.max_abs = mx; p.worst = mi; }
-  p.n_a += na; p.n_b += nb;
-  partials[blockIdx.x] = p;
-}
+using Partial = WorstPartial<uint64_t>;   // pass 1: a = voxels over the tolerance, b = NaN voxels; pass 2: both 0
 
 // ---- pass 1: max |q| per cell, the error before ----------------------------------------------------------------------------------------------
 template <typename T>
@@ -280,7 +138,7 @@ struct MeasureOp {
 #pragma unroll
     for (int j = 0; j < PieceOf<T>::n; ++j) {
       voxel(pc.v[j], i + j, x, y, z);
-      if (++x == (uint32_t)bx) { x = 0; if (++y == (uint32_t)by) { y = 0; ++z; } }   // (a dense grid: a piece may run over the end of a row)
+      next_voxel(bx, by, x, y, z);
     }
   }
 };
@@ -369,7 +227,7 @@ struct EncodeOp {
 #pragma unroll
     for (int j = 0; j < PieceOf<T>::n; ++j) {
       voxel(pc.v[j], i + j, x, y, z);
-      if (++x == (uint32_t)bx) { x = 0; if (++y == (uint32_t)by) { y = 0; ++z; } }
+      next_voxel(bx, by, x, y, z);
     }
   }
 };
@@ -383,7 +241,7 @@ __global__ void __launch_bounds__(kBlock) correction_encode_kernel(const T* __re
   for_each_chunk_voxel<const T>(ref, L, b, e, op);
   uint64_t na = 0, nb = 0;
   block_reduce(op.mx, op.mi, na, nb);
-  if (threadIdx.x == 0) merge_partial(partials, op.mx, op.mi, 0, 0);
+  if (threadIdx.x == 0) merge_partial<uint64_t>(partials, op.mx, op.mi, 0, 0);
 }
 
 // ---- the apply: decode, look up, correct, store ------------------------------------------------------------------------------------------------
@@ -434,7 +292,7 @@ struct ApplyOp {
 #pragma unroll
     for (int j = 0; j < PieceOf<T>::n; ++j) {
       pc.v[j] = voxel(i + j, x, y, z);
-      if (++x == (uint32_t)bx) { x = 0; if (++y == (uint32_t)by) { y = 0; ++z; } }
+      next_voxel(bx, by, x, y, z);
     }
     *reinterpret_cast<Piece<T>*>(p) = pc;   // one 16-byte vector store
   }
@@ -542,7 +400,7 @@ struct PlanesApplyOp {
 #pragma unroll
       for (int j = 0; j < N; ++j) {
         pc.v[j] = voxel(i + j, ox + x, oy + y, oz + z);
-        if (++x == (uint32_t)bx) { x = 0; if (++y == (uint32_t)by) { y = 0; ++z; } }
+        next_voxel(bx, by, x, y, z);
       }
     }
     *reinterpret_cast<Piece<T>*>(p) = pc;   // one 16-byte vector store
@@ -722,132 +580,6 @@ __global__ void __launch_bounds__(kBlock) correction_rate_final_kernel(const Rat
   if (threadIdx.x == 0) out[j] = RateSums{n_flagged, n_groups, payload, nbits, nonzero[j], refused};
 }
 
-// ---- host side: decode.hip's dispatch, validation and chunking ------------------------------------------------------------------------------
-template <typename F>
-void dispatch_type(int type, F&& f)
-{
-  switch (type) {
-  case 0: f((uint8_t*)nullptr); break;
-  case 1: f((int8_t*)nullptr); break;
-  case 2: f((uint16_t*)nullptr); break;
-  case 3: f((int16_t*)nullptr); break;
-  case 4: f((uint32_t*)nullptr); break;
-  case 5: f((int32_t*)nullptr); break;
-  case 8: f((float*)nullptr); break;
-  case 12: f((double*)nullptr); break;
-  default: throw std::runtime_error("unknown value type " + std::to_string(type));
-  }
-}
-
-// where the runtime knows the allocation a pointer lies in, what the call will touch must fit into it
-void require_room(const void* p, size_t bytes, const char* what)
-{
-  void* base = nullptr; size_t size = 0;
-  if (hipMemGetAddressRange((hipDeviceptr_t*)&base, &size, (hipDeviceptr_t)p) != hipSuccess || !base || !size) {
-    (void)hipGetLastError();   // not a pointer the runtime can place: taken as given
-    return;
-  }
-  const size_t room = (size_t)((const char*)base + size - (const char*)p);
-  if (bytes > room)
-    throw std::runtime_error(std::string(what) + " spans " + std::to_string(bytes) + " bytes from its device pointer, the allocation has " + std::to_string(room) + " left");
-}
-
-std::string str3(const int v[3]) { return std::to_string(v[0]) + " x " + std::to_string(v[1]) + " x " + std::to_string(v[2]); }
-
-// everything decode.hip refuses a box of the grid in the caller's array for, with its messages (box_lo = box_size = null: the whole
-// grid); returns the layout of the box in the caller's array and its lower corner
-BoxLayout validate_box_array(const void* data, int type, const int64_t* strides, const int box_lo[3], const int box_size[3], vec3i grid, vec3i& lower, float range_lo,
-                             float range_hi)
-{
-  if (!data) throw std::runtime_error("null device data");
-  const size_t ts = device_value_type_size(type);   // refuses the 64-bit integer and the vector types like the ingest
-  if (grid.x <= 0 || grid.y <= 0 || grid.z <= 0)
-    throw std::runtime_error("grid dimensions must be positive: " + std::to_string(grid.x) + " x " + std::to_string(grid.y) + " x " + std::to_string(grid.z));
-  if ((box_lo == nullptr) != (box_size == nullptr)) throw std::runtime_error("box_lo and box_size go together: both or neither");
-  lower = box_lo ? vec3i{box_lo[0], box_lo[1], box_lo[2]} : vec3i{0, 0, 0};
-  const vec3i size = box_size ? vec3i{box_size[0], box_size[1], box_size[2]} : grid;
-  if (size.x <= 0 || size.y <= 0 || size.z <= 0) throw std::runtime_error("box sizes must be positive: " + str3(box_size));
-  if (lower.x < 0 || lower.y < 0 || lower.z < 0 || (int64_t)lower.x + size.x > grid.x || (int64_t)lower.y + size.y > grid.y || (int64_t)lower.z + size.z > grid.z)
-    throw std::runtime_error("the box (lower " + str3(box_lo) + ", size " + str3(box_size) + ") is outside the grid " + std::to_string(grid.x) + " x " +
-                             std::to_string(grid.y) + " x " + std::to_string(grid.z));
-  const bool integer = type != 8 && type != 12;
-  if (!(range_lo < range_hi) && !(range_lo > range_hi)) throw std::runtime_error("range_lo == range_hi (or a NaN): an empty value range");
-  if (integer && range_lo > range_hi) throw std::runtime_error("an integer value type needs a value range (range_lo < range_hi)");
-
-  BoxLayout L{};
-  L.bx = (uint64_t)size.x; L.by = (uint64_t)size.y; L.bz = (uint64_t)size.z;
-  L.sx = strides ? strides[0] : 1;
-  L.sy = strides ? strides[1] : (int64_t)L.bx;
-  L.sz = strides ? strides[2] : (int64_t)(L.bx * L.by);
-  const int64_t s[3] = {L.sx, L.sy, L.sz};
-  const uint64_t n[3] = {L.bx, L.by, L.bz};
-  for (int a = 0; a < 3; ++a)
-    if (s[a] <= 0) throw std::runtime_error("strides must be positive: stride " + std::to_string(a) + " is " + std::to_string(s[a]));
-  // no two voxels at one address: the axes longer than one voxel, ordered by stride, must nest
-  int order[3] = {0, 1, 2};
-  std::sort(order, order + 3, [&](int a, int b) { return s[a] < s[b]; });
-  unsigned __int128 extent = 1, last = 0;   // elements the axes so far span; offset of the last voxel
-  for (int k = 0; k < 3; ++k) {
-    const int a = order[k];
-    if (n[a] == 1) continue;
-    if ((unsigned __int128)s[a] < extent)
-      throw std::runtime_error("the strides (" + std::to_string(L.sx) + ", " + std::to_string(L.sy) + ", " + std::to_string(L.sz) +
-                               ") overlap: two voxels of the box would share an address");
-    extent = (unsigned __int128)s[a] * (n[a] - 1) + extent;
-  }
-  for (int a = 0; a < 3; ++a) last += (unsigned __int128)s[a] * (n[a] - 1);
-  if ((last + 1) * ts > (unsigned __int128)INT64_MAX) throw std::runtime_error("the strides span more than 2^63 bytes");
-  if ((uintptr_t)data % ts != 0) throw std::runtime_error("device data is not aligned to its value type (" + std::to_string(ts) + " bytes)");
-  require_room(data, (size_t)((last + 1) * ts), "the box");
-
-  L.gather = L.sx != 1;
-  if (!L.gather) {
-    // contiguous runs: the whole box, whole slices, or x-rows
-    if (L.sy == (int64_t)L.bx && L.sz == (int64_t)(L.bx * L.by)) { L.run_len = L.bx * L.by * L.bz; L.runs_y = 1; L.sy = 0; L.sz = 0; }
-    else if (L.sy == (int64_t)L.bx) { L.run_len = L.bx * L.by; L.runs_y = 1; L.sy = 0; }
-    else { L.run_len = L.bx; L.runs_y = L.by; }
-  }
-  return L;
-}
-
-// launch width for the chunk [b, e): its pieces of work (for_each_chunk_voxel), the rest by block stride
-uint32_t chunk_grid(const BoxLayout& L, int type, uint64_t b, uint64_t e)
-{
-  uint64_t work = e - b;
-  if (!L.gather) {
-    const uint64_t per = 16 / device_value_type_size(type);
-    work = ((e - 1) / L.run_len - b / L.run_len + 1) * (1 + (std::min(L.run_len, e - b) + per - 1) / per);
-  }
-  const uint64_t blocks = (work + kBlock - 1) / kBlock;
-  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)Runtime::get().n_cus * 8));
-}
-
-uint64_t chunk_samples()
-{
-  uint64_t c = kDefaultChunk;
-  if (const char* e = std::getenv("VNR_AMD_DECODE_CHUNK")) {
-    char* end = nullptr;
-    const unsigned long long v = std::strtoull(e, &end, 10);
-    if (end == e || *end != '\0' || v == 0) throw std::runtime_error(std::string("VNR_AMD_DECODE_CHUNK must be a positive sample count, got '") + e + "'");
-    c = std::min<uint64_t>(v, kMaxChunk);
-  }
-  return c;
-}
-
-struct EventGuard {
-  hipEvent_t e = nullptr;
-  ~EventGuard() { if (e) (void)hipEventDestroy(e); }
-};
-
-// the library's stream waits for what the caller's stream holds at this point; the caller's stream is not touched otherwise
-void wait_for(hipStream_t theirs, hipStream_t ours, EventGuard& ev)
-{
-  if (!theirs) return;
-  VNR_HIP_CHECK(hipEventCreateWithFlags(&ev.e, hipEventDisableTiming));
-  VNR_HIP_CHECK(hipEventRecord(ev.e, theirs));
-  VNR_HIP_CHECK(hipStreamWaitEvent(ours, ev.e, 0));
-}
-
 Quantiser make_quantiser(uint32_t kind, double eps)
 {
   Quantiser k{kind, 0, 1, 1, 1.0};
@@ -922,7 +654,6 @@ std::shared_ptr<Correction> NeuralVolume::build_correction(const DeviceSource& r
   const uint32_t max_blocks = (uint32_t)Runtime::get().n_cus * 8;
   dd_coords_.ensure(3 * chunk);
   dd_values_.ensure(chunk);
-  static_assert(sizeof(Partial) == 4 * sizeof(double), "Partial is laid over dd_partials_");
   dd_partials_.ensure((size_t)(max_blocks + 1) * (sizeof(Partial) / sizeof(double)));
   Partial* partials = (Partial*)dd_partials_.ptr;
   Partial* d_result = partials + max_blocks;
@@ -932,7 +663,7 @@ std::shared_ptr<Correction> NeuralVolume::build_correction(const DeviceSource& r
   wait_for(ref.producer, stream, ev);   // the reference is complete once the caller's stream reaches this point
 
   // pass 1
-  correction_init_kernel<<<div_round_up(max_blocks, kBlock), kBlock, 0, stream>>>(partials, max_blocks);
+  worst_init_kernel<<<div_round_up(max_blocks, kBlock), kBlock, 0, stream>>>(partials, max_blocks);
   VNR_HIP_CHECK(hipGetLastError());
   cell_max.zero(stream);
   for (uint64_t b = 0; b < total; b += chunk) {
@@ -945,7 +676,7 @@ std::shared_ptr<Correction> NeuralVolume::build_correction(const DeviceSource& r
     });
     VNR_HIP_CHECK(hipGetLastError());
   }
-  correction_final_kernel<<<1, kBlock, 0, stream>>>(partials, max_blocks, d_result);
+  worst_final_kernel<<<1, kBlock, 0, stream>>>(partials, max_blocks, d_result);
   VNR_HIP_CHECK(hipGetLastError());
   Partial before;
   std::vector<uint32_t> cells(n_cells);
@@ -963,8 +694,8 @@ std::shared_ptr<Correction> NeuralVolume::build_correction(const DeviceSource& r
     corr->data.cells.push_back(CorrectionCellEntry{(uint32_t)cl, width});
     payload_bytes += correction_padded_bytes(correction_cell_voxels(dims, (uint32_t)cl), width);
   }
-  corr->n_voxels_flagged = before.n_a;
-  corr->n_nan = before.n_b;
+  corr->n_voxels_flagged = before.a;
+  corr->n_nan = before.b;
   corr->max_abs_before = before.max_abs < 0.0 ? std::numeric_limits<double>::quiet_NaN() : before.max_abs;
   Partial after = before;   // without a flagged cell every voxel stays as decoded
   if (!corr->data.cells.empty()) {
@@ -973,7 +704,7 @@ std::shared_ptr<Correction> NeuralVolume::build_correction(const DeviceSource& r
     corr->d_payload.resize(payload_bytes);
     corr->d_payload.zero(stream);   // (the padding, and what no voxel owns, stays zero)
     // pass 2: the network a second time
-    correction_init_kernel<<<div_round_up(max_blocks, kBlock), kBlock, 0, stream>>>(partials, max_blocks);
+    worst_init_kernel<<<div_round_up(max_blocks, kBlock), kBlock, 0, stream>>>(partials, max_blocks);
     VNR_HIP_CHECK(hipGetLastError());
     for (uint64_t b = 0; b < total; b += chunk) {
       const uint64_t e = std::min(total, b + chunk);
@@ -986,7 +717,7 @@ std::shared_ptr<Correction> NeuralVolume::build_correction(const DeviceSource& r
       });
       VNR_HIP_CHECK(hipGetLastError());
     }
-    correction_final_kernel<<<1, kBlock, 0, stream>>>(partials, max_blocks, d_result);
+    worst_final_kernel<<<1, kBlock, 0, stream>>>(partials, max_blocks, d_result);
     VNR_HIP_CHECK(hipGetLastError());
     VNR_HIP_CHECK(hipMemcpyAsync(&after, d_result, sizeof(after), hipMemcpyDeviceToHost, stream));
     corr->data.payload.resize(payload_bytes);

@@ -61,7 +61,7 @@ The --round-trip times are host clocks as well, each around one call that return
 "error" are the whole calls (coordinate kernel + evaluation + store or reduce kernel per chunk of VNR_AMD_DECODE_CHUNK samples),
 "inference" is one vnrAmdNeuralVolumeInference call + synchronise over the same voxel centres as ready-made coordinates, so
 "decode - inference" is a difference of wall times.  Each is run once to warm up, then --repeat times.  The kernels are decode_coords_kernel, decode_store_kernel,
-decode_error_kernel and decode_error_final_kernel.
+decode_error_kernel and worst_final_kernel<double>.
 
 The --error-bound times are host clocks around whole calls in the same way: "build" evaluates the network twice and brings the codes
 to the host, "apply" evaluates it once.  The kernels are correction_measure_kernel, correction_encode_kernel and

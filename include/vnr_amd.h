@@ -613,9 +613,16 @@ int  vnrAmdRendererSetInShaderKernel(vnrAmdRenderer, int mode);
  * per-iteration duration (ms) of the sample-evaluation kernel in the last profiled frame */
 int  vnrAmdRendererDebugQueues(vnrAmdRenderer, const float** d_coords, const uint32_t** d_counters, float* iteration_ms, int max_iterations);
 /* diagnostics: the schedule the last sample-streaming frame ran with: out = {samples per ray and iteration (N_ITERS, method_raymarching.cu:30-40),
- * ray parts, 1 = survivors packed inside the evaluation kernel, 1 = decoupled walk / evaluate / compose loop}.  Tests use it to know WHICH path
- * they compared with the oracle (a rank's small share runs another schedule than a whole frame). */
+ * ray parts, 1 = done inside the evaluation kernel: the survivors of an iteration are numbered (dense ray -> list slot) by that kernel's
+ * prologue, for parts of every size; 0 = by a kernel of its own behind the evaluation (volumes without a network, 128-neuron models),
+ * 1 = decoupled walk / evaluate / compose loop}.  Tests use it to know WHICH path they compared with the oracle (a rank's small share runs
+ * another schedule than a whole frame). */
 int  vnrAmdRendererDebugSchedule(vnrAmdRenderer, int out[4]);
+/* diagnostics: the numbering of an iteration's surviving rays on its own (pack_rays.h), as the kernel behind the evaluation runs it.
+ * n_in > 0: rays the march consumed; counts[g], g < ceil(n_in / 64): what it leaves per 64-ray group, survivors in the low byte (the
+ * bytes above it belong to the frame statistics).  Host arrays in and out: src_out (room for n_in entries) receives the list slot
+ * 64 g + l of the dense rays 0 .. alive, alive_out the published number of them. */
+int  vnrAmdDebugRaySourceIndex(const uint32_t* counts, uint32_t n_in, uint32_t* src_out, uint32_t* alive_out);
 void vnrAmdReleaseRenderer(vnrAmdRenderer);
 
 /* ---- multi-GPU: one process per GPU (new work; the reference is single-GPU, its only device-selection code is

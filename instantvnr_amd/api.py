@@ -835,6 +835,19 @@ def renderer_schedule(r):
     return {"n_iters": out[0], "n_parts": out[1], "fused_pack": bool(out[2]), "decoupled": bool(out[3])}
 
 
+def ray_source_index(counts, n_in):
+    """the numbering of a march's surviving rays, run on its own (vnrAmdDebugRaySourceIndex): counts[ceil(n_in / 64)] as the march packs
+    them (survivors of a 64-ray group in the low byte) -> (list slot of every dense ray, published alive count)"""
+    n_in = int(n_in)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    if n_in <= 0 or counts.shape != ((n_in + 63) // 64,):
+        raise ValueError("counts must hold one entry per 64-ray group of n_in > 0 rays")
+    src = np.zeros(n_in, dtype=np.uint32)
+    alive = C.c_uint32()
+    check(lib().vnrAmdDebugRaySourceIndex(counts.ctypes.data, n_in, src.ctypes.data, C.byref(alive)))
+    return src[:alive.value].copy(), int(alive.value)
+
+
 def neural_brick_image(v):
     """state of the de-hashed inference copy of the hashed levels (csrc/network.h)"""
     u, b, ms = C.c_int(), C.c_size_t(), C.c_float()

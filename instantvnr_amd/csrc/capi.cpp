@@ -1063,6 +1063,10 @@ int vnrAmdRendererDebugSchedule(vnrAmdRenderer r, int out[4])
     for (int i = 0; i < 4; ++i) out[i] = v[i];
   });
 }
+int vnrAmdDebugRaySourceIndex(const uint32_t* counts, uint32_t n_in, uint32_t* src_out, uint32_t* alive_out)
+{
+  return guarded([&]() { debug_ray_source_index(counts, n_in, src_out, alive_out); });
+}
 int vnrAmdRendererSetProfiling(vnrAmdRenderer r, int e) { return guarded([&]() { VNR_REN(r); r->r->set_profiling(e != 0); }); }
 int vnrAmdRendererSetAsync(vnrAmdRenderer r, int e) { return guarded([&]() { VNR_REN(r); r->r->set_async(e != 0); }); }
 int vnrAmdRendererSetInShaderKernel(vnrAmdRenderer r, int m) { return guarded([&]() { VNR_REN(r); r->r->set_in_shader_kernel(m); }); }

@@ -152,8 +152,8 @@ public:
   // for a kernel that evaluates the network inside its own loop (the in-shader ray marcher, in_shader.h): levels (brick image
   // policy applied, as for an inference launch on `s`), table, weight image.  false: this model is not one of the MFMA kernels' shapes
   bool tile_net(TileNet* out, hipStream_t s) const;
-  // `pack` (pack_rays.h): the ray marcher's packing of the iteration, run as a prologue of the evaluation kernel; -> false when this
-  // model's kernel cannot take it (the caller then launches the packing kernel itself)
+  // `pack` (pack_rays.h): the ray marcher's numbering of the iteration's surviving rays, run as a prologue of the evaluation kernel;
+  // -> false when this model's kernel cannot take it (the caller then launches it as a kernel of its own)
   bool inference_queue(const float* d_records, float* d_out, uint32_t out_stride, const uint32_t* d_n, size_t n_max, hipStream_t s,
                        uint32_t sharers = 1, const PackArgs* pack = nullptr) const;
   // encode only: fp16 [n][padded_width]

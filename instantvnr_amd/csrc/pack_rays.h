@@ -1,6 +1,7 @@
-// pack_rays.h — the ray lists of the streaming marcher and the packing of their survivors (render.hip), as a device function so that it
-// can run either as a kernel of its own (compact_rays_kernel) or as the prologue of the evaluation kernel of the same iteration
-// (network_infer.hip: both only need what march(it) wrote, and a small share of the frame is a chain of short launches).
+// pack_rays.h — the ray lists of the streaming marcher (render.hip) and the indexing of their survivors, as a device function so that it
+// can run either as the prologue of the evaluation kernel of the same iteration (network_infer.hip: both only need what march(it) wrote,
+// and the prologue costs the chain march -> evaluate -> march no launch) or, where there is no such kernel, as a kernel
+// of its own behind the evaluation (ray_index_kernel).  No ray is moved: march(it + 1) is told where dense ray i lives.
 #pragma once
 #include "common.h"
 
@@ -19,7 +20,7 @@ struct RayList {  // per ray payload, SoA (RayMarchingData, method_raymarching.c
 };
 
 // SINGLE_SHADE_HEURISTIC only (inter_highest_*, method_raymarching.cu:84-87): per ray, the sample that has contributed most so
-// far; [0] belongs to the dense ray list, [1] to the scratch list.  A kernel argument of its own, behind the others, so that
+// far; [b] belongs to ray list b.  A kernel argument of its own, behind the others, so that
 // the instances that never touch it do not drag it through their scalar registers: as members of RayList these six pointers
 // cost the unshaded march kernel 6 more spilled SGPRs (90 -> 96) and the bench 3 % of its frame rate (A/B on one box,
 // tools/ab/ab.sh, n = 3 each: 195-198 against 201-204 frames/s; 199-200 against 199-201 with this layout).
@@ -33,27 +34,37 @@ struct SshLists {
 enum { C_RAYS0 = 0, C_RAYS1 = 1, C_SAMPLES0 = 2, C_SAMPLES1 = 3, C_HIT = 4, C_STAT_SAMPLES = 6, C_STAT_REFRAYS = 8, C_COUNT = 16 };
 
 struct PackArgs {
-  RayList src, dst;              // scratch list march(it) left its survivors in (group g: slots 64 g ..), dense list of march(it + 1)
+  uint32_t* ray_src;             // out: dense ray index of march(it + 1) -> slot of the list march(it) left its survivors in (group g: slots 64 g ..)
   const uint32_t* ray_counts;    // per 64-ray group: survivors | rays alive when the march began to emit << 8
   uint32_t n_first;              // rays of the first march (it = 0)
   uint32_t* counters;
-  int parity, first, ssh, grad;
-  SshLists ssh_lists;
+  int parity, first, grad;
   uint32_t* host_alive;          // pinned: alive rays after this iteration
   uint32_t* host_stats;          // pinned copy of the counters
-  uint32_t n_blocks;             // work items of pack_rays_block<WAVES> (scratch slots / (64 WAVES)); 0: nothing to pack
+  uint32_t item_groups;          // 64-ray groups per work item of pack_rays_block (pack_item_groups)
+  uint32_t n_blocks;             // work items (pack_items); 0: nothing to index
 };
 
+// Groups per work item for a part of n_rays rays.  Every item sums the counts of all groups before it, so the items of a part read
+// (items x groups / 2) counts between them: at 4 groups per item, 2 048 items x 4 096 counts on average for half the bench frame, 25 us of
+// every evaluation kernel that carried them (profiles/r07_ray_index_ab.txt).  A large part takes the most one wave scan covers, 64 (128
+// items for that half frame); a small one, whose evaluation kernel is a few blocks per CU and short, keeps many light items.
+inline uint32_t pack_item_groups(uint32_t n_rays) { return n_rays > 262144u ? 64u : 4u; }
+inline uint32_t pack_items(uint32_t n_rays) { return ((n_rays + 255u) / 256u * 4u + pack_item_groups(n_rays) - 1u) / pack_item_groups(n_rays); }
+
 #if defined(__HIPCC__)
-// Packs the 64-ray groups march_kernel left in the scratch list (group g holds ray_counts[g] rays in slots 64 g ..) into the
-// dense list, in group order.  One thread per scratch slot; a work item (WAVES groups, one block of 64 WAVES threads) first sums the
+// Numbers the survivors march_kernel left in its list (group g holds ray_counts[g] rays in slots 64 g ..) in group order: dense ray
+// base(g) + l of the next march is slot 64 g + l, one 4-byte store per survivor and no copy of its 60 bytes of state
+// (88 with the single-shade lists).  A work item (a.item_groups groups, a multiple of WAVES and at most 64, dealt over the waves of one
+// block of 64 WAVES threads) first sums the
 // counts of all groups before it (at most 64 KiB of L2-resident counts), so no second launch and no dependency between items is
 // needed.  The item that holds the last group publishes the number of alive rays; item 0 also clears the sample counter the next
 // march adds to.  s_part: WAVES words of LDS; every thread of the block calls this with the same `item`.
 template <int WAVES>
 __device__ __forceinline__ void pack_rays_block(const PackArgs& a, uint32_t item, uint32_t* s_part)
 {
-  constexpr uint32_t T = 64u * WAVES;  // threads = scratch slots per item; WAVES groups
+  constexpr uint32_t T = 64u * WAVES;
+  const uint32_t G = a.item_groups;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   uint32_t* counters = a.counters;
   const int parity = a.parity;
@@ -67,7 +78,7 @@ __device__ __forceinline__ void pack_rays_block(const PackArgs& a, uint32_t item
     if (item == 0 && tid >= C_HIT && tid < C_COUNT) a.host_stats[tid] = counters[tid];
     return;
   }
-  const uint32_t g0 = item * (uint32_t)WAVES;
+  const uint32_t g0 = item * G;
   if (g0 >= n_groups) return;
   const uint32_t* __restrict__ ray_counts = a.ray_counts;
   // a group's count: survivors in the low byte, rays that were alive when the march began to emit above it
@@ -80,38 +91,23 @@ __device__ __forceinline__ void pack_rays_block(const PackArgs& a, uint32_t item
   uint32_t before = 0;
 #pragma unroll
   for (int w = 0; w < WAVES; ++w) before += s_part[w];
-  // counts of this item's groups: lane l < WAVES of every wave holds count[g0 + l]
-  const uint32_t mine = (lane < (uint32_t)WAVES && g0 + lane < n_groups) ? ray_counts[g0 + lane] & 0xffu : 0u;
+  // counts of this item's groups: lane l < G of every wave holds count[g0 + l]
+  const uint32_t mine = (lane < G && g0 + lane < n_groups) ? ray_counts[g0 + lane] & 0xffu : 0u;
   uint32_t incl = mine;
 #pragma unroll
-  for (int d = 1; d < WAVES; d <<= 1) {
+  for (int d = 1; d < 64; d <<= 1) {
     const uint32_t y = __shfl_up(incl, d);
     if ((int)lane >= d) incl += y;
   }
-  const uint32_t count = __shfl(mine, (int)wave), base = before + __shfl(incl, (int)wave) - count;
-  const uint32_t block_total = __shfl(incl, WAVES - 1);
-  const bool last_block = g0 + (uint32_t)WAVES >= n_groups;  // (block-uniform) the item that holds the last group
+  const uint32_t block_total = __shfl(incl, 63);
+  const bool last_block = g0 + G >= n_groups;  // (block-uniform) the item that holds the last group
   if (last_block && tid == 0) { counters[C_RAYS0 + (parity ^ 1)] = before + block_total; *a.host_alive = before + block_total; }
-  if (lane < count) {
-    const RayList& src = a.src;
-    const RayList& dst = a.dst;
-    const uint32_t from = ((g0 + wave) << 6) + lane, to = base + lane;
-    dst.pixel_index[to] = src.pixel_index[from];
-    dst.jitter[to] = src.jitter[from];
-    dst.alpha[to] = src.alpha[from];
-    dst.color[to] = src.color[from];
-    dst.cell[to] = src.cell[from];
-    dst.t_next[to] = src.t_next[from];
-    dst.next_cell_begin[to] = src.next_cell_begin[from];
-    dst.sample_base[to] = src.sample_base[from];
-    dst.sample_count[to] = src.sample_count[from];
-    if (a.ssh) {  // scratch [1] -> dense [0]
-      const SshLists& sl = a.ssh_lists;
-      sl.org[0][to] = sl.org[1][from]; sl.color[0][to] = sl.color[1][from]; sl.alpha[0][to] = sl.alpha[1][from];
-    }
+  for (uint32_t l = wave; l < G; l += (uint32_t)WAVES) {  // (block-uniform bounds) group g0 + l: one thread per slot
+    const uint32_t count = __shfl(mine, (int)l), base = before + __shfl(incl, (int)l) - count;
+    if (lane < count) a.ray_src[base + lane] = ((g0 + l) << 6) + lane;
   }
   // Frame statistics of the march that just ran (it used to count them with three device-scope atomics per wave), summed by
-  // the last item after its copies so that the code needs no more registers than the copies do
+  // the last item after its stores
   if (last_block) {
     uint32_t asum = 0;
     for (uint32_t g = tid; g < n_groups; g += T) asum += ray_counts[g] >> 8;

@@ -9,7 +9,7 @@
 //    N_ITERS x R slots -> compose kernel (walks the DDA a second time) -> 4-byte D2H + stream sync.
 //  * here one fused `march` kernel per iteration composes the previous batch of a ray and immediately emits its
 //    next batch (one DDA walk per iteration, ray state stays in registers in between), rays are compacted with
-//    wave64 ballot + popcount, and SAMPLES are compacted with a wave prefix sum, so the network only ever sees
+//    wave64 ballot + popcount inside their 64-ray group and numbered across groups by an index (pack_rays.h), and SAMPLES are compacted with a wave prefix sum, so the network only ever sees
 //    live samples (the reference infers stale slots).  Sample (t0,t1) pairs are staged in LDS while a lane walks.
 //  * the sample count never visits the host: the fused inference kernel reads it from device memory; the host
 //    launches the iteration count of the previous frame speculatively and only then looks at a pinned counter.
@@ -47,8 +47,10 @@ namespace vnr {
 // that contributed most and its result goes to the per-pixel hand-over arrays instead of the frame; M_SHADOW is the second
 // pass, one ray per pixel from that sample towards the light, alpha only, which finally shades and writes the pixel
 // (method_raymarching.cu:789-833, 877-900, 960-973).
+// cur / nxt: the ray list the march before this one wrote and the one this march writes (the two lists of a part swap roles every
+// iteration, launch_iteration); ssh_lists: [0] goes with cur, [1] with nxt.  Dense ray i of this march lives in slot ray_src[i] of cur.
 template <bool FIRST, int MODE>
-__global__ void __launch_bounds__(256) march_kernel(const RenderParams p, const RayList cur, const RayList nxt,
+__global__ void __launch_bounds__(256) march_kernel(const RenderParams p, const uint32_t* __restrict__ ray_src, const RayList cur, const RayList nxt,
                                                     const vec2f* __restrict__ vd_in, vec4f* __restrict__ queue,
                                                     vec2f* __restrict__ vd_out, uint32_t* __restrict__ counters,
                                                     uint32_t* __restrict__ ray_counts, int parity, const SshLists ssh_lists,
@@ -144,17 +146,20 @@ __global__ void __launch_bounds__(256) march_kernel(const RenderParams p, const 
           }
         }
       } else {
-        pixel = cur.pixel_index[i];
-        jitter = cur.jitter[i];
-        alpha = cur.alpha[i];
-        color = cur.color[i];
-        it.cell = cur.cell[i];
-        it.t_next = cur.t_next[i];
-        it.next_cell_begin = cur.next_cell_begin[i];
-        const uint32_t sb = cur.sample_base[i], sc = cur.sample_count[i];
+        // where the march before left this ray: the survivors of a 64-ray group stay in the group's slots and only their numbering is dense
+        // (pack_rays.h), so a wave reads a few runs of neighbouring slots
+        const uint32_t s = ray_src[i];
+        pixel = cur.pixel_index[s];
+        jitter = cur.jitter[s];
+        alpha = cur.alpha[s];
+        color = cur.color[s];
+        it.cell = cur.cell[s];
+        it.t_next = cur.t_next[s];
+        it.next_cell_begin = cur.next_cell_begin[s];
+        const uint32_t sb = cur.sample_base[s], sc = cur.sample_count[s];
         if (MODE == M_SHADOW) { org = color; dir = p.shadow_dir; }   // compute_ray<SHADOW> (:639-653)
         else compute_ray(p, pixel, org, dir);
-        if (MODE == M_SSH) { h_org = ssh_lists.org[0][i]; h_color = ssh_lists.color[0][i]; h_alpha = ssh_lists.alpha[0][i]; }
+        if (MODE == M_SSH) { h_org = ssh_lists.org[0][s]; h_color = ssh_lists.color[0][s]; h_alpha = ssh_lists.alpha[0][s]; }
         m_dir = dir * p.mc_rcp;
         intersect_box(tmin, tmax, org, dir, p.bbox_lo, p.bbox_hi);
         // compose (classification, opacity correction, front-to-back blending)
@@ -249,7 +254,7 @@ __global__ void __launch_bounds__(256) march_kernel(const RenderParams p, const 
     // the march the host expects to be the frame's last is launched without evaluation and packing behind it and reports here (pinned
     // host memory) whether that expectation held (launch_iteration)
     if (tail_flag && lane == 0 && wave_rays) *tail_flag = 1u;
-    // Surviving rays go to the wave's OWN 64 slots of the scratch list (`nxt`) and compact_rays_kernel packs the groups in
+    // Surviving rays go to the wave's OWN 64 slots of `nxt` and pack_rays_block numbers the groups' survivors in
     // wave order afterwards: an order-preserving compaction, so a 64-ray group stays a compact patch of the image over the
     // iterations.  (Claiming slots with an atomic, as the reference does, hands them out in wave-arrival order; by the third
     // iteration a group then mixes rays of distant tiles and the hash-grid gathers of its samples lose 20-35 % of their rate.)
@@ -257,7 +262,7 @@ __global__ void __launch_bounds__(256) march_kernel(const RenderParams p, const 
     // Sample slots: ONE claim per block.  A device-scope atomic is resolved beyond the per-XCD L2, and atomics on one address
     // are served one after the other (about 10 ns each, measured: a first march of 131 072 pixels whose waves each issued four
     // of them took 45 us before tracing a single ray), so neither the claim is made per wave nor are the frame statistics
-    // counted here: compact_rays_kernel sums them from the per-group counts.
+    // counted here: pack_rays_block sums them from the per-group counts.
     // The queue counter counts RECORDS (what the evaluation kernel reads); with 4 records per sample every claim is a
     // multiple of 4, so claim / 4 is a unique sample-slot base.
     uint32_t* claim = s_claim + 8u * (trip & 1u);
@@ -367,12 +372,12 @@ __global__ void gt_sample_kernel(const uint32_t* __restrict__ n_ptr, const float
   }
 }
 
-// pack_rays_block (pack_rays.h) as a kernel of its own: ground-truth volumes, models outside the MFMA kernels' shapes, parts of more than 262 144 rays
-template <int WAVES>
-__global__ void __launch_bounds__(64 * WAVES) compact_rays_kernel(const PackArgs a)
+// pack_rays_block (pack_rays.h) as a kernel of its own, where the evaluation kernel does not run it as its prologue: ground-truth volumes,
+// 128-neuron models (evaluation blocks of 8 waves).  The same items of 256 threads as the prologue, one block each.
+__global__ void __launch_bounds__(256) ray_index_kernel(const PackArgs a)
 {
-  __shared__ uint32_t s_part[WAVES];
-  pack_rays_block<WAVES>(a, blockIdx.x, s_part);
+  __shared__ uint32_t s_part[4];
+  pack_rays_block<4>(a, blockIdx.x, s_part);
 }
 
 // ------------------------------------------------------------------------------------------------ monolithic marcher (mode 4)
@@ -614,7 +619,7 @@ __global__ void pt_monolithic_kernel(const RenderParams p)
   write_pixel(p, {r.L.x, r.L.y, r.L.z, 1.0f}, pixel);
 }
 
-// packs the survivors in group order (compact_rays_kernel's scheme) and writes one queue record per alive ray:
+// packs the survivors in group order (pack_rays_block's prefix scheme, with the copy) and writes one queue record per alive ray:
 // {sample_coord, index of the ray} -> the evaluation kernel puts the value where the next pt_kernel reads it
 __global__ void __launch_bounds__(1024) pt_compact_kernel(const PtRays src, const PtRays dst, const uint32_t* __restrict__ ray_counts,
                                                           uint32_t n_first, uint32_t* __restrict__ counters, int parity, int first,
@@ -676,8 +681,9 @@ struct PartState {
   vec2f* vd[2];
   uint32_t* c;         // device counters of this half
   uint32_t* rc;        // survivors per 64-ray group
-  uint32_t* hc;        // pinned ring of alive-ray counts (written by compact_rays_kernel)
-  uint32_t* hs;        // pinned copy of this half's counters as of the last compact_rays_kernel
+  uint32_t* ray_src;   // dense ray index -> slot of the list the last march wrote (written inside eval(it), read by march(it + 1))
+  uint32_t* hc;        // pinned ring of alive-ray counts (written by pack_rays_block)
+  uint32_t* hs;        // pinned copy of this half's counters as of the last pack_rays_block
   hipStream_t s;
   size_t s_max;
   uint32_t it = 0, used = 0;
@@ -934,6 +940,7 @@ void Renderer::ensure_queues(size_t n_pixels, int n_iters, bool gradient)
   const bool grad = gradient || queue_grad_;
   // everything x 2: two frame slots (renderer.h)
   q_u32_.resize(2 * 6 * P);
+  ray_src_.resize(2 * P);
   ray_counts_.resize(2 * (P / 64 + 64 + 8 * kMaxParts));   // survivors per 64-ray group (P is a multiple of 64; slack for the round-up to 256 rays)
   q_f32_.resize(2 * 18 * P);
   q_i32_.resize(2 * 6 * P);
@@ -1287,15 +1294,19 @@ void Renderer::launch_iteration(StreamingFrame& f, int h)
     const bool skip_tail = it >= 1 && it + 1 == f.predicted[h] && it + 1 < max_iterations;
     uint32_t* tail_flag = nullptr;
     if (skip_tail) { hf.hs[0] = 0; tail_flag = hf.hs; }   // hs[0 .. C_HIT) is not used by the packing kernel's statistics
-    // march(it): reads the dense ray list rl[0] (count: counter `parity`), leaves the survivors of every 64-ray group in the
-    // group's slots of the scratch list rl[1] and appends their samples to queue `parity`
+    // march(it): reads its rays (count: counter `parity`) through ray_src from the list march(it - 1) wrote, rl[parity], leaves the
+    // survivors of every 64-ray group in the group's slots of the other list, rl[parity ^ 1], and appends their samples to queue `parity`
     {
+      const RayList& cur = hf.rl[parity];
+      const RayList& nxt = hf.rl[parity ^ 1];
+      SshLists sl;   // [0]: read, [1]: written
+      for (int b = 0; b < 2; ++b) { sl.org[b] = hf.ssh.org[parity ^ b]; sl.color[b] = hf.ssh.color[parity ^ b]; sl.alpha[b] = hf.ssh.alpha[parity ^ b]; }
       const bool first = it == 0;
       const uint32_t blocks = std::min<uint32_t>(div_round_up(P, 256), first ? 4096u : 2048u);
       const size_t lds = first ? shmem : shmem_compose;
       const vec2f* vd_in = hf.vd[parity ^ 1];
       vec2f* vd_out = hf.vd[parity];
-#define VNR_MARCH(FIRST_, MODE_) march_kernel<FIRST_, MODE_><<<blocks, 256, lds, s_it>>>(hf.p, hf.rl[0], hf.rl[1], vd_in, hf.queue, vd_out, c, hf.rc, parity, hf.ssh, tail_flag)
+#define VNR_MARCH(FIRST_, MODE_) march_kernel<FIRST_, MODE_><<<blocks, 256, lds, s_it>>>(hf.p, hf.ray_src, cur, nxt, vd_in, hf.queue, vd_out, c, hf.rc, parity, sl, tail_flag)
       switch (pass_mode) {
       case M_GRADIENT: if (first) VNR_MARCH(true, M_GRADIENT); else VNR_MARCH(false, M_GRADIENT); break;
       case M_SSH: if (first) VNR_MARCH(true, M_SSH); else VNR_MARCH(false, M_SSH); break;
@@ -1327,23 +1338,19 @@ void Renderer::launch_tail(StreamingFrame& f, int h, uint32_t it, hipStream_t s_
 {
   PartState* half = f.part;
   const int H = f.H;
-  const bool grad = f.grad, ssh = f.ssh;
+  const bool grad = f.grad;
   NeuralVolume* nv = f.nv;
   {
     PartState& hf = half[h];
     const int parity = (int)(it & 1u);
     const uint32_t P = hf.p.n_local;
     uint32_t* c = hf.c;
-    // the packing of march(it)'s survivors into rl[0] in group order (count -> counter `parity^1`; clears the sample counter of march(it+1)):
-    // as a prologue of the evaluation kernel when that is one of the MFMA kernels, else a kernel of its own behind it
+    // the numbering of march(it)'s survivors in group order (ray_src; count -> counter `parity^1`; clears the sample counter of march(it+1)):
+    // as a prologue of the evaluation kernel when that is one of the MFMA kernels with 4-wave blocks, else a kernel of its own behind it
     PackArgs pk;
-    pk.src = hf.rl[1]; pk.dst = hf.rl[0]; pk.ray_counts = hf.rc; pk.n_first = P; pk.counters = c; pk.parity = parity; pk.first = it == 0 ? 1 : 0;
-    pk.ssh = ssh ? 1 : 0; pk.grad = grad ? 1 : 0; pk.ssh_lists = hf.ssh; pk.host_alive = hf.hc + (it & 255u); pk.host_stats = hf.hs;
-    pk.n_blocks = div_round_up(P, 256);
-    // Only where the launch it saves is on the critical path, i.e. a part of at most 262 144 rays (a 1/2 .. 1/8 share of the bench frame):
-    // a whole frame's packing kernel runs under the other part's evaluation kernel, the frame takes the same time either way, and the
-    // evaluation kernel's own time (what bench.py's roofline is computed from) would carry the packing's 15-20 us per launch.
-    const bool fused_pack = P <= 262144u;
+    pk.ray_src = hf.ray_src; pk.ray_counts = hf.rc; pk.n_first = P; pk.counters = c; pk.parity = parity; pk.first = it == 0 ? 1 : 0;
+    pk.grad = grad ? 1 : 0; pk.host_alive = hf.hc + (it & 255u); pk.host_stats = hf.hs;
+    pk.item_groups = pack_item_groups(P); pk.n_blocks = pack_items(P);
     bool packed = false;
     if (!s_it) s_it = hf.s;
     if (profiling_) VNR_HIP_CHECK(hipEventRecord(events_[f.slot][h][2 * it], s_it));
@@ -1356,26 +1363,50 @@ void Renderer::launch_tail(StreamingFrame& f, int h, uint32_t it, hipStream_t s_
     } else if (nv) {
       // a record's 4th word is the float index of its result in this arena (stride 1)
       packed = nv->network().inference_queue((const float*)hf.queue, (float*)hf.vd[parity], 1, c + C_SAMPLES0 + parity, hf.s_max, s_it, (uint32_t)H,
-                                             fused_pack ? &pk : nullptr);
+                                             &pk);
     } else {
       const uint32_t blocks = std::min<uint32_t>(div_round_up(hf.s_max, 256), (uint32_t)Runtime::get().n_cus * 8u);
       gt_sample_kernel<<<blocks, 256, 0, s_it>>>(c + C_SAMPLES0 + parity, hf.p.volume, hf.p.vol_dims, hf.queue, (float*)hf.vd[parity]);
     }
     if (profiling_) VNR_HIP_CHECK(hipEventRecord(events_[f.slot][h][2 * it + 1], s_it));
     last_schedule_[2] = packed ? 1 : 0;
-    if (!packed) {
-      // 1024-thread blocks need 4 free wave slots on every SIMD of one CU at once, which the other half's evaluation kernel
-      // rarely leaves: a small share (where the wait shows) packs with 256-thread blocks
-      constexpr uint32_t kCompactSmallLimit = 262144u;
-      if (P <= kCompactSmallLimit) {
-        compact_rays_kernel<4><<<pk.n_blocks, 256, 0, s_it>>>(pk);
-      } else {
-        pk.n_blocks = div_round_up(P, 1024);
-        compact_rays_kernel<16><<<pk.n_blocks, 1024, 0, s_it>>>(pk);
-      }
-    }
+    if (!packed) ray_index_kernel<<<pk.n_blocks, 256, 0, s_it>>>(pk);
     VNR_HIP_CHECK(hipGetLastError());
   }
+}
+
+// diagnostics (vnrAmdDebugRaySourceIndex): ray_index_kernel alone on the counts of a first march of n_in rays
+void debug_ray_source_index(const uint32_t* counts, uint32_t n_in, uint32_t* src_out, uint32_t* alive_out)
+{
+  if (!counts || !src_out || !alive_out) throw std::runtime_error("null argument");
+  if (n_in == 0) throw std::runtime_error("no rays");
+  if (n_in > (1u << 30)) throw std::runtime_error("too many rays");
+  if (!Runtime::get().ready()) Runtime::get().init(-1);
+  const hipStream_t s = Runtime::get().stream;
+  const uint32_t n_given = div_round_up(n_in, 64), n_groups = div_round_up(n_in, 256) * 4u;   // the march writes a count for every group of its last block
+  std::vector<uint32_t> h(n_groups, 0u);
+  for (uint32_t g = 0; g < n_given; ++g) {
+    const uint32_t room = std::min(64u, n_in - 64u * g);
+    if ((counts[g] & 0xffu) > room) throw std::runtime_error("group " + std::to_string(g) + " counts more survivors than it has rays");
+    h[g] = counts[g];
+  }
+  DeviceBuffer<uint32_t> d_counts, d_src, d_words;
+  d_counts.upload(h.data(), n_groups, s);
+  d_src.resize((size_t)n_groups * 64);
+  d_words.resize(2 * C_COUNT + 1);   // counters, the copy the kernel publishes, the alive count
+  d_words.zero(s);
+  PackArgs pk;
+  pk.ray_src = d_src.ptr; pk.ray_counts = d_counts.ptr; pk.n_first = n_in; pk.counters = d_words.ptr; pk.parity = 0; pk.first = 1; pk.grad = 0;
+  pk.host_stats = d_words.ptr + C_COUNT; pk.host_alive = d_words.ptr + 2 * C_COUNT;
+  pk.item_groups = pack_item_groups(n_in); pk.n_blocks = pack_items(n_in);   // (as for a ray part of n_in rays)
+  ray_index_kernel<<<pk.n_blocks, 256, 0, s>>>(pk);
+  VNR_HIP_CHECK(hipGetLastError());
+  uint32_t words[2 * C_COUNT + 1];
+  d_words.download(words, 2 * C_COUNT + 1, s);
+  const uint32_t alive = words[2 * C_COUNT];
+  if (alive > n_in || alive != words[C_RAYS1]) throw std::runtime_error("internal: the index kernel published " + std::to_string(alive) + " alive rays of " + std::to_string(n_in));
+  d_src.download(src_out, alive, s);
+  *alive_out = alive;
 }
 
 void Renderer::render_streaming(const RenderParams& p_all, int pass_mode, bool defer)
@@ -1461,6 +1492,7 @@ void Renderer::render_streaming(const RenderParams& p_all, int pass_mode, bool d
     hf.queue = queue_base + rec_per_slot * off * QI;
     hf.c = counters_base + (size_t)h * C_COUNT;
     hf.rc = rc_base + off / 64 + (size_t)h * 8;   // halves are multiples of 64 rays; 8 groups of slack each
+    hf.ray_src = ray_src_.ptr + (size_t)slot * QP + off;
     hf.hc = host_base + (size_t)h * 256;
     hf.hs = host_base + kMaxParts * 256 + (size_t)h * C_COUNT;
     if (h > 0 && !part_streams_[h]) part_streams_[h] = Runtime::get().part_stream(h);
@@ -1569,7 +1601,7 @@ void Renderer::finish_streaming(StreamingFrame& f)
     while (used > 1 && hf.hc[(used - 2) & 255u] == 0) --used;  // trailing speculative no-op iterations
     predicted[h] = used;
     hf.used = used;
-    const uint32_t* hc = hf.hs;   // every march of the frame ran before the last compact_rays_kernel
+    const uint32_t* hc = hf.hs;   // every march of the frame ran before the last pack_rays_block
     if (pass_mode != M_SHADOW) stats_.n_rays_hit += hc[C_HIT];
     n_samples += (uint64_t)hc[C_STAT_SAMPLES] | ((uint64_t)hc[C_STAT_SAMPLES + 1] << 32);
     n_refrays += (uint64_t)hc[C_STAT_REFRAYS] | ((uint64_t)hc[C_STAT_REFRAYS + 1] << 32);

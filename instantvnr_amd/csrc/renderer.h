@@ -57,7 +57,7 @@ public:
   const float* debug_coords() { finish_pending(); return (const float*)queue_.ptr; }  // 16-byte records {x, y, z, slot}
   const uint32_t* debug_counters() { finish_pending(); return counters_.ptr; }
   const std::vector<float>& debug_iteration_ms() { finish_pending(); return iter_ms_; }
-  // which schedule the last streaming frame ran: {samples per ray and iteration, ray parts, 1 = packing fused into the evaluation kernel, 1 = decoupled loop}
+  // which schedule the last streaming frame ran: {samples per ray and iteration, ray parts, 1 = survivors numbered inside the evaluation kernel, 1 = decoupled loop}
   const int* debug_schedule() { finish_pending(); return last_schedule_; }
   // rank `part` of `parts` renders the pixel blocks b with b % parts == part (block = `block` consecutive pixels)
   void set_pixel_interleave(uint32_t block, uint32_t parts, uint32_t part)
@@ -183,6 +183,7 @@ private:
   DeviceBuffer<uint32_t> q_u32_;   // pixel_index[2], sample_base[2], sample_count[2]
   DeviceBuffer<float> q_f32_;      // jitter[2], alpha[2], color[2][3], t_next[2][3], next_cell_begin[2]
   DeviceBuffer<int> q_i32_;        // cell[2][3]
+  DeviceBuffer<uint32_t> ray_src_; // dense ray index of the next march -> slot of the list the last march wrote (pack_rays.h)
   DeviceBuffer<float> q_ssh_;      // single-shade heuristic: highest org[2][3], colour[2][3], alpha[2] per ray
   DeviceBuffer<float> pt_rays_, pt_values_;   // path tracing: 2 x 26 planes of ray state, one value per alive ray
   uint32_t predicted_pt_ = 0;
@@ -200,5 +201,9 @@ private:
   std::vector<float> iter_ms_;
   int last_schedule_[4] = {0, 0, 0, 0};
 };
+
+// diagnostics: the numbering of a march's survivors (pack_rays.h) as the kernel of its own, on host arrays: counts[ceil(n_in / 64)] as the
+// march packs them -> src_out[0 .. *alive_out)
+void debug_ray_source_index(const uint32_t* counts, uint32_t n_in, uint32_t* src_out, uint32_t* alive_out);
 
 }  // namespace vnr

@@ -623,6 +623,11 @@ int  vnrAmdRendererDebugSchedule(vnrAmdRenderer, int out[4]);
  * bytes above it belong to the frame statistics).  Host arrays in and out: src_out (room for n_in entries) receives the list slot
  * 64 g + l of the dense rays 0 .. alive, alive_out the published number of them. */
 int  vnrAmdDebugRaySourceIndex(const uint32_t* counts, uint32_t n_in, uint32_t* src_out, uint32_t* alive_out);
+/* diagnostics: what the evaluation kernel the dispatcher launches for inference was compiled to, by model shape: F features per level, K_IN padded
+ * encoding width, W neurons, general != 0 for a model outside the common kind (rarer grid types, interpolations, activations).  regs: vector
+ * registers per lane (96 or fewer let five waves share a SIMD), scratch_bytes: private memory per lane (0 = nothing spilled), lds_bytes: static
+ * LDS of a block (the weight image is dynamic LDS and not counted).  Any output may be NULL. */
+int  vnrAmdDebugEvalKernelResources(uint32_t F, uint32_t K_IN, uint32_t W, int general, int* regs, int* scratch_bytes, int* lds_bytes);
 void vnrAmdReleaseRenderer(vnrAmdRenderer);
 
 /* ---- multi-GPU: one process per GPU (new work; the reference is single-GPU, its only device-selection code is

@@ -213,6 +213,7 @@ def lib():
     sig("vnrAmdRendererDebugQueues", I, P, C.POINTER(P), C.POINTER(P), FP, I)
     sig("vnrAmdRendererDebugSchedule", I, P, IP)
     sig("vnrAmdDebugRaySourceIndex", I, P, U32, P, C.POINTER(U32))
+    sig("vnrAmdDebugEvalKernelResources", I, U32, U32, U32, I, IP, IP, IP)
     sig("vnrAmdReleaseRenderer", None, P)
     sig("vnrAmdDistGetUniqueId", I, P)
     sig("vnrAmdDistInit", I, I, I, I, P, C.c_char_p, C.c_char_p)

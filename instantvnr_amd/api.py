@@ -848,6 +848,15 @@ def ray_source_index(counts, n_in):
     return src[:alive.value].copy(), int(alive.value)
 
 
+def eval_kernel_resources(n_features, padded_width, n_neurons, general=False):
+    """what the evaluation kernel instance of a model shape was compiled to (vnrAmdDebugEvalKernelResources): vector registers per lane
+    (96 or fewer: five waves per SIMD), scratch bytes per lane, static LDS bytes per block"""
+    regs, scratch, lds = C.c_int(), C.c_int(), C.c_int()
+    check(lib().vnrAmdDebugEvalKernelResources(int(n_features), int(padded_width), int(n_neurons), int(bool(general)),
+                                               C.byref(regs), C.byref(scratch), C.byref(lds)))
+    return {"regs": regs.value, "scratch_bytes": scratch.value, "lds_bytes": lds.value}
+
+
 def neural_brick_image(v):
     """state of the de-hashed inference copy of the hashed levels (csrc/network.h)"""
     u, b, ms = C.c_int(), C.c_size_t(), C.c_float()

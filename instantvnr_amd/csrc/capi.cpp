@@ -1067,6 +1067,10 @@ int vnrAmdDebugRaySourceIndex(const uint32_t* counts, uint32_t n_in, uint32_t* s
 {
   return guarded([&]() { debug_ray_source_index(counts, n_in, src_out, alive_out); });
 }
+int vnrAmdDebugEvalKernelResources(uint32_t F, uint32_t K_IN, uint32_t W, int general, int* regs, int* scratch_bytes, int* lds_bytes)
+{
+  return guarded([&]() { eval_kernel_resources(F, K_IN, W, general != 0, regs, scratch_bytes, lds_bytes); });
+}
 int vnrAmdRendererSetProfiling(vnrAmdRenderer r, int e) { return guarded([&]() { VNR_REN(r); r->r->set_profiling(e != 0); }); }
 int vnrAmdRendererSetAsync(vnrAmdRenderer r, int e) { return guarded([&]() { VNR_REN(r); r->r->set_async(e != 0); }); }
 int vnrAmdRendererSetInShaderKernel(vnrAmdRenderer r, int m) { return guarded([&]() { VNR_REN(r); r->r->set_in_shader_kernel(m); }); }

@@ -52,6 +52,9 @@ __global__ void __launch_bounds__(64 * MlpShape<W>::WAVES) fused_infer_kernel(co
 {
   constexpr int NCHUNK = K_IN / 8;  // half8 chunks of the feature vector
   constexpr uint32_t WAVES = MlpShape<W>::WAVES;
+  // the common inference instances are kept within 96 registers, five waves per SIMD; what that takes is compiled into them alone,
+  // every other instance is the code it was
+  constexpr bool DIET = MODE == 0 && !GENERAL;
   extern __shared__ __attribute__((aligned(16))) half_t lds[];
 
   const uint32_t lane = threadIdx.x & 63u;
@@ -99,7 +102,7 @@ __global__ void __launch_bounds__(64 * MlpShape<W>::WAVES) fused_infer_kernel(co
     if (args.queue_mode) {  // ray marcher's sample queue: one 16-byte load per sample
       const uint4_t rec = ((const uint4_t*)args.coords)[ic];
       p = {__uint_as_float(rec.x), __uint_as_float(rec.y), __uint_as_float(rec.z)};
-      out_index = rec.w * args.out_stride;
+      if (!DIET) out_index = rec.w * args.out_stride;
     } else {
       p = ((const float3_packed*)args.coords)[ic];
       if (args.dest) out_index = args.dest[ic];
@@ -110,7 +113,7 @@ __global__ void __launch_bounds__(64 * MlpShape<W>::WAVES) fused_infer_kernel(co
     // points where this kernel's throughput would take 5: 73.8 us.  Those 8.4 M random 4-byte reads are 8.4 M distinct 64-byte sectors,
     // 0.54 GB in 67 us = 8 TB/s: the pass is at the memory system's sector rate, not waiting on a chain of round trips.  Removed.)
     half8_t feat[NCHUNK];
-    encode_tile<F, K_IN, GENERAL>(args.levels, args.n_levels, args.interpolation, rsrc, args.brick_image, p.x, p.y, p.z, feat,
+    encode_tile<F, K_IN, GENERAL, DIET>(args.levels, args.n_levels, args.interpolation, rsrc, args.brick_image, p.x, p.y, p.z, feat,
                                   GENERAL ? args.quantize_threshold : 0.0f);
 
     if (MODE != 0 && args.features_out && i < n) {
@@ -127,11 +130,24 @@ __global__ void __launch_bounds__(64 * MlpShape<W>::WAVES) fused_infer_kernel(co
     else
       y = mlp_tile<W, K_IN, MODE == 2, GENERAL>((const half_t*)lds, feat, nh, act, h, r, args.acts_out, n, tile * 64u);
     // network output is produced in half precision (output activation on the half), then cast to float (tcnn_impl.cu:421-431)
-    if (i < n) args.out[out_index] = finish_output<GENERAL>(y, args.output_activation);
+    if (DIET) {
+      // the record's destination is read again here, 4 bytes that hit the L2, and the sample index computed again from an opaque copy of the
+      // tile: neither is carried in a register across encode and MLP
+      uint32_t tile_again = tile;
+      asm volatile("" : "+v"(tile_again));
+      const uint32_t j = tile_again * 64u + lane;
+      if (args.queue_mode) out_index = ((const uint32_t*)args.coords)[(size_t)min(j, n - 1u) * 4u + 3u] * args.out_stride;
+      else if (!args.dest) out_index = j;
+      if (j < n) args.out[out_index] = finish_output<GENERAL>(y, args.output_activation);
+    } else if (i < n) args.out[out_index] = finish_output<GENERAL>(y, args.output_activation);
   }
 }
 
 // ------------------------------------------------------------------------------------------------
+// resident blocks per CU of a launch that reads the brick image and whose sample count the host knows (launch_one): alone on the GPU / beside a
+// second evaluation kernel
+constexpr uint32_t kBlocksPerCuAlone = 5, kBlocksPerCuShared = 4;
+
 template <int F, int K_IN, int W, int MODE, bool GENERAL>
 static void launch_one(const InferArgs& a, size_t n_max, hipStream_t s)
 {
@@ -139,13 +155,18 @@ static void launch_one(const InferArgs& a, size_t n_max, hipStream_t s)
   const Runtime& rt = Runtime::get();
   const uint32_t n_tiles = div_round_up(n_max, 64);
   uint32_t blocks = div_round_up(n_tiles, WAVES);
-  // persistent blocks of 4 waves; 113 registers allow 4 per CU.  How many pay depends on what limits the kernel (MI355X, C4
-  // bench frame, kernel-only G samples/s):
-  //   reading the hashed parameter blob (bound by fetched lines): 4 blocks 5.98, 3 blocks 6.20, 2 blocks 6.25, 1 block 4.77
-  //   reading the brick image (2.4 x fewer lines, latency matters again), one stream: 2 blocks 8.1, 3 blocks 10.1, 4 blocks 11.1;
-  //   two ray halves on two streams (two of these kernels share the GPU): 2 blocks 179, 3 blocks 195, 4 blocks 192 frames/s
-  // so the caller says how many kernels share the GPU (`sharers`): 4 blocks alone, 3 with a second stream.
-  // VNR_AMD_INFER_BLOCKS_PER_CU (1..4) overrides, for diagnostics.
+  // persistent blocks of 4 waves; the 94 registers of the bench instance (F 2, 16 levels, 64 neurons) allow 5 per CU, five waves per SIMD
+  // (100 registers and 4 until the level count and the last layer's operands stopped living across the whole tile loop).
+  // How many pay depends on what limits the kernel (MI355X, C4 bench frame, kernel-only G samples/s):
+  //   reading the hashed parameter blob (bound by fetched lines), 113 registers: 4 blocks 5.98, 3 blocks 6.20, 2 blocks 6.25, 1 block 4.77;
+  //     94 registers, one stream: 3 blocks 9.00, 4 blocks 8.72, 5 blocks 8.19 (blocks handed out by the hardware, below: 9.17)
+  //   reading the brick image (2.4 x fewer lines, latency matters again), one stream, 113 registers: 2 blocks 8.1, 3 blocks 10.1, 4 blocks 11.1;
+  //     94 registers: 3 blocks 11.53, 4 blocks 13.17, 5 blocks 13.71
+  //   two ray halves on two streams (two of these kernels share the GPU), 113 registers: 2 blocks 179, 3 blocks 195, 4 blocks 192 frames/s;
+  //     94 registers: 3 blocks 265.7, 4 blocks 270.2, 5 blocks 273.2 frames/s (profiles/r08_five_waves.txt has the parent's rows beside these)
+  // so the caller says how many kernels share the GPU (`sharers`): reading the image, 5 blocks alone and 4 with a second stream, where the
+  // instance fits them; reading the blob, 4 and 3 as before.
+  // VNR_AMD_INFER_BLOCKS_PER_CU (1..64) overrides, for diagnostics.
   static const uint32_t forced = [] {
     const char* e = std::getenv("VNR_AMD_INFER_BLOCKS_PER_CU");
     const int v = e ? std::atoi(e) : 0;
@@ -153,8 +174,20 @@ static void launch_one(const InferArgs& a, size_t n_max, hipStream_t s)
   }();
   const size_t shmem = (MODE == 1 || a.weights_global) ? 16 : (size_t)a.lds_halves * sizeof(uint16_t);
   // (128 neurons: the image takes most of the LDS, one block of 8 waves per CU)
-  const uint32_t fit = (uint32_t)std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / std::max<size_t>(shmem, 1)));
-  uint32_t max_blocks = (uint32_t)rt.n_cus * (forced ? forced : std::min(fit, a.sharers >= 2 ? 3u : 4u));
+  auto kernel = fused_infer_kernel<F, K_IN, W, MODE, GENERAL>;
+  // blocks of this instance a CU holds: by its registers (512 per SIMD lane in granules of 8, at most 8 waves; a block puts WAVES / 4 waves
+  // on each SIMD) and by the LDS its weight image takes.  Never below the 4 every instance was launched with before the bench instance
+  // came down to 96 registers: the instances above 128 registers (GENERAL, wide encodings, 128 neurons) keep the grids they had.
+  static const uint32_t fit_regs = [&] {
+    hipFuncAttributes at{};
+    VNR_HIP_CHECK(hipFuncGetAttributes(&at, (const void*)kernel));
+    const uint32_t waves = std::min(8u, 512u / std::max(8u, next_multiple((uint32_t)at.numRegs, 8u)));
+    return MODE == 0 ? std::max(4u, waves * 4u / WAVES) : 4u;   // (the policy below was measured for inference launches)
+  }();
+  const uint32_t fit = (uint32_t)std::max<size_t>(1, std::min<size_t>(fit_regs, (160 * 1024) / std::max<size_t>(shmem, 1)));
+  // (without the brick image the fifth block costs, 8.72 -> 8.19: such launches keep the 4 / 3 they had)
+  const uint32_t policy = a.brick_image ? (a.sharers >= 2 ? kBlocksPerCuShared : kBlocksPerCuAlone) : (a.sharers >= 2 ? 3u : 4u);
+  uint32_t max_blocks = (uint32_t)rt.n_cus * (forced ? forced : std::min(fit, policy));
   // The ray marcher's queue (count on the device, n_max an upper bound of which a frame fills 25-30 %): more blocks than fit,
   // so that the hardware hands them out as room appears.  With a second kernel and the march kernels of the other ray half
   // on the GPU a resident grid of fixed size either leaves room unused or waits for it with its tiles already dealt out.
@@ -163,7 +196,6 @@ static void launch_one(const InferArgs& a, size_t n_max, hipStream_t s)
   if (!forced && a.n_ptr && a.queue_mode) max_blocks = std::min((uint32_t)rt.n_cus * 32u, std::max((uint32_t)rt.n_cus * 4u, n_tiles / 33u));
   if (blocks > max_blocks) blocks = max_blocks;
   blocks = next_multiple(blocks, 8);
-  auto kernel = fused_infer_kernel<F, K_IN, W, MODE, GENERAL>;
   static bool attr_set = false;
   if (!attr_set) {
     VNR_HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -173,17 +205,35 @@ static void launch_one(const InferArgs& a, size_t n_max, hipStream_t s)
   VNR_HIP_CHECK(hipGetLastError());
 }
 
+// the encoding shapes (F, padded width) the kernels are instantiated for
+#define VNR_ENCODING_SHAPES(X)                                                                                  \
+  X(1, 16) X(1, 32)                                                                                             \
+  X(2, 16) X(2, 32) X(2, 48) X(2, 64)                                                                           \
+  X(4, 16) X(4, 32) X(4, 48) X(4, 64) X(4, 80) X(4, 96) X(4, 112) X(4, 128)                                     \
+  X(8, 16) X(8, 32) X(8, 48) X(8, 64) X(8, 80) X(8, 96) X(8, 112) X(8, 128)
+
+[[noreturn]] static void unsupported_shape(uint32_t F, uint32_t K_IN)
+{
+  throw std::runtime_error("unsupported encoding shape: n_features_per_level=" + std::to_string(F) + " padded width=" + std::to_string(K_IN));
+}
+
 template <int W, int MODE, bool GENERAL>
 static void dispatch(uint32_t F, uint32_t K_IN, const InferArgs& a, size_t n_max, hipStream_t s)
 {
-#define VNR_CASE(f, k) if (F == f && K_IN == k) return launch_one<f, k, W, MODE, GENERAL>(a, n_max, s)
-  VNR_CASE(1, 16); VNR_CASE(1, 32);
-  VNR_CASE(2, 16); VNR_CASE(2, 32); VNR_CASE(2, 48); VNR_CASE(2, 64);
-  VNR_CASE(4, 16); VNR_CASE(4, 32); VNR_CASE(4, 48); VNR_CASE(4, 64); VNR_CASE(4, 80); VNR_CASE(4, 96); VNR_CASE(4, 112); VNR_CASE(4, 128);
-  VNR_CASE(8, 16); VNR_CASE(8, 32); VNR_CASE(8, 48); VNR_CASE(8, 64); VNR_CASE(8, 80); VNR_CASE(8, 96); VNR_CASE(8, 112); VNR_CASE(8, 128);
+#define VNR_CASE(f, k) if (F == f && K_IN == k) return launch_one<f, k, W, MODE, GENERAL>(a, n_max, s);
+  VNR_ENCODING_SHAPES(VNR_CASE)
 #undef VNR_CASE
-  throw std::runtime_error("unsupported encoding shape: n_features_per_level=" + std::to_string(F) +
-                           " padded width=" + std::to_string(K_IN));
+  unsupported_shape(F, K_IN);
+}
+
+// what the instance `dispatch` would launch was compiled to (vnrAmdDebugEvalKernelResources): registers per lane, scratch and static LDS
+template <int W, int MODE, bool GENERAL>
+static void dispatch_attributes(uint32_t F, uint32_t K_IN, hipFuncAttributes* out)
+{
+#define VNR_CASE(f, k) if (F == f && K_IN == k) { VNR_HIP_CHECK(hipFuncGetAttributes(out, (const void*)fused_infer_kernel<f, k, W, MODE, GENERAL>)); return; }
+  VNR_ENCODING_SHAPES(VNR_CASE)
+#undef VNR_CASE
+  unsupported_shape(F, K_IN);
 }
 
 // one translation unit per width and kind (network_infer_w*.hip) instantiates the inference and the training-forward kernels
@@ -192,6 +242,7 @@ static void dispatch(uint32_t F, uint32_t K_IN, const InferArgs& a, size_t n_max
   {                                                                                                                       \
     if (mode == 0) dispatch<W, 0, GENERAL>(F, K_IN, a, n_max, s);                                                         \
     else dispatch<W, 2, GENERAL>(F, K_IN, a, n_max, s);                                                                   \
-  }
+  }                                                                                                                       \
+  void fused_attributes_w##W##SUFFIX(uint32_t F, uint32_t K_IN, hipFuncAttributes* out) { dispatch_attributes<W, 0, GENERAL>(F, K_IN, out); }
 
 }  // namespace vnr

@@ -179,6 +179,10 @@ __device__ __forceinline__ float mlp_column_tile(const half_t* __restrict__ wgt,
   }
 
   // last layer: output neuron 0 only (the other 15 padded rows are never read)
+  // (the barrier keeps the scheduler from loading the last layer's 16 registers of weights before the hidden layers, where they would sit beside
+  // accumulators, features and A operands at the kernel's register peak: 100 -> 96 registers for the bench instance.  Common instances only: the
+  // GENERAL ones stay as they were compiled before)
+  if (!GENERAL) __builtin_amdgcn_sched_barrier(0);
   const half_t* wl = wgt + S1 * Sh::STEP + nh * Sh::HIDDEN;
   float part = 0.0f;
 #pragma unroll
@@ -197,7 +201,8 @@ __device__ __forceinline__ float mlp_column_tile(const half_t* __restrict__ wgt,
 
 // ---- encode: lane = sample, level wave-uniform -> feat[K_IN / 8] (the sample's K_IN features, fp16, zero padded) ---------------
 
-template <int F, int K_IN, bool GENERAL = false>
+// SPLIT: unroll the levels as two loops (below); the evaluation kernel's common inference instances ask for it
+template <int F, int K_IN, bool GENERAL = false, bool SPLIT = false>
 __device__ __forceinline__ void encode_tile(const LevelInfo* levels, uint32_t n_levels, uint32_t interpolation, const table_rsrc_t& rsrc,
                                             const uint8_t* brick_image, float x, float y, float z, half8_t (&feat)[K_IN / 8],
                                             float quantize_threshold = 0.0f)
@@ -210,6 +215,9 @@ __device__ __forceinline__ void encode_tile(const LevelInfo* levels, uint32_t n_
   const LevelInfo* lvtab_generic = levels;
   asm volatile("" : "+s"(lvtab_generic));
   const const_levels_t lvtab = (const_levels_t)lvtab_generic;
+  // The level count likewise: left loop-invariant, each of the L_PAD `l < n_levels` tests is hoisted into a scalar register pair of its own (32 SGPRs
+  // for 16 levels), and what no longer fits the scalar file moves into vector registers for the whole persistent loop.
+  if (!GENERAL) asm volatile("" : "+s"(n_levels));
   // wave-uniform by construction; say so, or hipcc wraps every buffer load in a waterfall loop
   auto level_consts = [&](int l) {
     LevelInfo lv;
@@ -223,17 +231,28 @@ __device__ __forceinline__ void encode_tile(const LevelInfo* levels, uint32_t n_
     lv.pad1 = __builtin_amdgcn_readfirstlane(lvtab[l].pad1);
     return lv;
   };
-#pragma unroll
-  for (int l = 0; l < L_PAD; ++l) {
-    half_t o[F];
-#pragma unroll
-    for (int f = 0; f < F; ++f) o[f] = (half_t)0.0f;
-    if (l < (int)n_levels) encode_level_fast<F, GENERAL>(level_consts(l), interpolation, rsrc, brick_image, x, y, z, o, quantize_threshold);
-#pragma unroll
-    for (int f = 0; f < F; ++f) feat[(l * F + f) / 8][(l * F + f) % 8] = o[f];
-    // keep the level constants (scalar registers) of at most four levels live at a time
-    if ((l & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+  // one level: its F features into `feat`; the level constants (scalar registers) of at most four levels are kept live at a time
+#define VNR_ENCODE_ONE_LEVEL(l)                                                                                                              \
+  {                                                                                                                                          \
+    half_t o[F];                                                                                                                             \
+    _Pragma("unroll") for (int f = 0; f < F; ++f) o[f] = (half_t)0.0f;                                                                       \
+    if (l < (int)n_levels) encode_level_fast<F, GENERAL>(level_consts(l), interpolation, rsrc, brick_image, x, y, z, o, quantize_threshold); \
+    _Pragma("unroll") for (int f = 0; f < F; ++f) feat[(l * F + f) / 8][(l * F + f) % 8] = o[f];                                             \
+    if ((l & 3) == 3) __builtin_amdgcn_sched_barrier(0);                                                                                     \
   }
+  if constexpr (SPLIT && L_PAD > 16) {
+    // two loops of 16 levels and the rest, not one of up to 32: the compiler unrolls a loop on request only up to a size that 32 levels of the
+    // common instances exceed, and a loop left rolled indexes `feat` by a variable, which puts the whole feature vector into scratch memory
+    // (272 bytes per lane for F = 4 with 32 levels)
+#pragma unroll
+    for (int l = 0; l < 16; ++l) VNR_ENCODE_ONE_LEVEL(l)
+#pragma unroll
+    for (int l = 16; l < L_PAD; ++l) VNR_ENCODE_ONE_LEVEL(l)
+  } else {
+#pragma unroll
+    for (int l = 0; l < L_PAD; ++l) VNR_ENCODE_ONE_LEVEL(l)
+  }
+#undef VNR_ENCODE_ONE_LEVEL
 }
 
 // ---- MLP on the wave's 64 samples: feat (consumed) -> this lane's sample's output, before the final rounding to fp16 ------------

@@ -325,5 +325,7 @@ public:
 
 // layout helpers shared with tests
 uint32_t grid_make_layout(const ModelConfig& cfg, GridDevice* out);
+// diagnostics (network_infer.hip): registers per lane, scratch bytes per lane and static LDS bytes of the inference kernel instance of a model shape
+void eval_kernel_resources(uint32_t F, uint32_t K_IN, uint32_t W, bool general, int* regs, int* scratch_bytes, int* lds_bytes);
 
 }  // namespace vnr

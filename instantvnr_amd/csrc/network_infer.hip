@@ -94,6 +94,26 @@ void launch_pack_mlp(const uint16_t* params, uint16_t* packed, uint16_t* packedT
 VNR_DECL(launch_fused_w16); VNR_DECL(launch_fused_w32); VNR_DECL(launch_fused_w64); VNR_DECL(launch_fused_w128);
 VNR_DECL(launch_fused_w16g); VNR_DECL(launch_fused_w32g); VNR_DECL(launch_fused_w64g); VNR_DECL(launch_fused_w128g);
 #undef VNR_DECL
+#define VNR_DECL(name) void name(uint32_t F, uint32_t K_IN, hipFuncAttributes* out)
+VNR_DECL(fused_attributes_w16); VNR_DECL(fused_attributes_w32); VNR_DECL(fused_attributes_w64); VNR_DECL(fused_attributes_w128);
+VNR_DECL(fused_attributes_w16g); VNR_DECL(fused_attributes_w32g); VNR_DECL(fused_attributes_w64g); VNR_DECL(fused_attributes_w128g);
+#undef VNR_DECL
+
+// diagnostics (vnrAmdDebugEvalKernelResources): what the inference instance of a model shape was compiled to
+void eval_kernel_resources(uint32_t F, uint32_t K_IN, uint32_t W, bool general, int* regs, int* scratch_bytes, int* lds_bytes)
+{
+  hipFuncAttributes at{};
+  switch (W) {
+  case 16: general ? fused_attributes_w16g(F, K_IN, &at) : fused_attributes_w16(F, K_IN, &at); break;
+  case 32: general ? fused_attributes_w32g(F, K_IN, &at) : fused_attributes_w32(F, K_IN, &at); break;
+  case 64: general ? fused_attributes_w64g(F, K_IN, &at) : fused_attributes_w64(F, K_IN, &at); break;
+  case 128: general ? fused_attributes_w128g(F, K_IN, &at) : fused_attributes_w128(F, K_IN, &at); break;
+  default: throw std::runtime_error("no MFMA kernel for n_neurons = " + std::to_string(W));
+  }
+  if (regs) *regs = at.numRegs;
+  if (scratch_bytes) *scratch_bytes = (int)at.localSizeBytes;
+  if (lds_bytes) *lds_bytes = (int)at.sharedSizeBytes;
+}
 
 void launch_fused(int mode, const GridDevice& grid, uint32_t in_width, const FusedMlp& mlp, const LevelInfo* d_levels, const uint16_t* table, size_t table_bytes,
                   const float* coords, float* out, uint16_t* features_out, uint16_t* acts_out, size_t n, const uint32_t* d_n, size_t n_max, hipStream_t s,

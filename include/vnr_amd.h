@@ -618,6 +618,19 @@ int  vnrAmdRendererDebugQueues(vnrAmdRenderer, const float** d_coords, const uin
  * 1 = decoupled walk / evaluate / compose loop}.  Tests use it to know WHICH path they compared with the oracle (a rank's small share runs
  * another schedule than a whole frame). */
 int  vnrAmdRendererDebugSchedule(vnrAmdRenderer, int out[4]);
+/* The same report by name, with where the last frame's compose kernels read the transfer function: the streaming loops (coupled and
+ * decoupled) keep the colour and the opacity table in LDS while the pair fits tfn_lds_bytes (16 bytes per colour, 4 per opacity: 1228
+ * entries each for tables of equal length) and read them from global memory above that; the same lookup either way.  tfn_in_lds is
+ * decided by the transfer function of the frame rendered last, whatever its rendering mode (the other modes always read global memory). */
+typedef struct vnrAmdSchedule {
+  int n_iters;        /* samples per ray and iteration */
+  int n_parts;        /* ray parts */
+  int fused_pack;     /* 1 = survivors numbered inside the evaluation kernel */
+  int decoupled;      /* 1 = decoupled walk / evaluate / compose loop */
+  int tfn_in_lds;     /* 1 = both transfer function tables in LDS, 0 = read from global memory */
+  int tfn_lds_bytes;  /* the budget that decides it */
+} vnrAmdSchedule;
+int  vnrAmdRendererGetSchedule(vnrAmdRenderer, vnrAmdSchedule*);
 /* diagnostics: the numbering of an iteration's surviving rays on its own (pack_rays.h), as the kernel behind the evaluation runs it.
  * n_in > 0: rays the march consumed; counts[g], g < ceil(n_in / 64): what it leaves per 64-ray group, survivors in the low byte (the
  * bytes above it belong to the frame statistics).  Host arrays in and out: src_out (room for n_in entries) receives the list slot

@@ -40,6 +40,11 @@ def build(force=False):
     return SO_PATH
 
 
+class Schedule(C.Structure):
+    _fields_ = [("n_iters", C.c_int), ("n_parts", C.c_int), ("fused_pack", C.c_int), ("decoupled", C.c_int), ("tfn_in_lds", C.c_int),
+                ("tfn_lds_bytes", C.c_int)]
+
+
 class FrameStats(C.Structure):
     _fields_ = [("n_samples", C.c_uint64), ("n_reference_slots", C.c_uint64), ("n_iterations", C.c_uint32),
                 ("n_rays_hit", C.c_uint32), ("infer_kernel_ms", C.c_double), ("infer_kernel_launches", C.c_uint64), ("infer_union_ms", C.c_double)]
@@ -212,6 +217,7 @@ def lib():
     sig("vnrAmdRendererSetInShaderKernel", I, P, I)
     sig("vnrAmdRendererDebugQueues", I, P, C.POINTER(P), C.POINTER(P), FP, I)
     sig("vnrAmdRendererDebugSchedule", I, P, IP)
+    sig("vnrAmdRendererGetSchedule", I, P, C.POINTER(Schedule))
     sig("vnrAmdDebugRaySourceIndex", I, P, U32, P, C.POINTER(U32))
     sig("vnrAmdDebugEvalKernelResources", I, U32, U32, U32, I, IP, IP, IP)
     sig("vnrAmdReleaseRenderer", None, P)

@@ -828,11 +828,16 @@ def vnrRendererGetFrameStats(r):
     return {k: getattr(s, k) for k, _ in s._fields_}
 
 
-def renderer_schedule(r):
-    """which schedule the last sample-streaming frame ran (vnrAmdRendererDebugSchedule)"""
-    out = (C.c_int * 4)()
-    check(lib().vnrAmdRendererDebugSchedule(r.h, out))
-    return {"n_iters": out[0], "n_parts": out[1], "fused_pack": bool(out[2]), "decoupled": bool(out[3])}
+def renderer_schedule(r, tables=False):
+    """which schedule the last sample-streaming frame ran (vnrAmdRendererGetSchedule); tables=True adds the report's transfer-function part:
+    "tfn_in_lds", whether the last frame's colour and opacity tables fit the compose kernels' LDS budget, and that budget, "tfn_lds_bytes"
+    (callers compare the four scheduling keys as a whole, so the two are given on request)"""
+    s = _lib.Schedule()
+    check(lib().vnrAmdRendererGetSchedule(r.h, C.byref(s)))
+    out = {"n_iters": s.n_iters, "n_parts": s.n_parts, "fused_pack": bool(s.fused_pack), "decoupled": bool(s.decoupled)}
+    if tables:
+        out.update(tfn_in_lds=bool(s.tfn_in_lds), tfn_lds_bytes=s.tfn_lds_bytes)
+    return out
 
 
 def ray_source_index(counts, n_in):

@@ -1063,6 +1063,17 @@ int vnrAmdRendererDebugSchedule(vnrAmdRenderer r, int out[4])
     for (int i = 0; i < 4; ++i) out[i] = v[i];
   });
 }
+int vnrAmdRendererGetSchedule(vnrAmdRenderer r, vnrAmdSchedule* out)
+{
+  return guarded([&]() {
+    VNR_REN(r);
+    if (!out) throw std::runtime_error("null output");
+    const int* v = r->r->debug_schedule();
+    out->n_iters = v[0]; out->n_parts = v[1]; out->fused_pack = v[2]; out->decoupled = v[3];
+    out->tfn_in_lds = r->r->tfn_in_lds() ? 1 : 0;
+    out->tfn_lds_bytes = (int)Renderer::kTfnLdsBytes;
+  });
+}
 int vnrAmdDebugRaySourceIndex(const uint32_t* counts, uint32_t n_in, uint32_t* src_out, uint32_t* alive_out)
 {
   return guarded([&]() { debug_ray_source_index(counts, n_in, src_out, alive_out); });

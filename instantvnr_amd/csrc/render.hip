@@ -1028,7 +1028,8 @@ void Renderer::render()
   p.mc_rcp = {1.0f / sp.x, 1.0f / sp.y, 1.0f / sp.z};
   p.mc_max_opacity = mc.d_max_opacity();
   p.tfn = tfn_.view();
-  p.tfn_in_lds = ((size_t)p.tfn.n_colors * sizeof(vec4f) + (size_t)p.tfn.n_alphas * sizeof(float)) <= 24 * 1024 ? 1u : 0u;
+  p.tfn_in_lds = ((size_t)p.tfn.n_colors * sizeof(vec4f) + (size_t)p.tfn.n_alphas * sizeof(float)) <= kTfnLdsBytes ? 1u : 0u;
+  last_tfn_in_lds_ = p.tfn_in_lds != 0;
   // A small SHARE of a frame (one rank of 8) is bound by the latency of the per-iteration kernel chain, not by throughput:
   // fewer, longer iterations (tools/share_probe.py, 1/8 of the bench frame: 24 -> 0.995 ms, 32 -> 0.910 ms, 48 -> 0.905 ms in round 1; round 5: 1/8 share
   // 24 -> 0.592, 32 -> 0.536, 40 -> 0.578, 48 -> 0.61 ms; 1/4 share 24 -> 1.028, 32 -> 1.006 ms; 1/3 share 24 -> 1.323, 32 -> 1.338 ms: 32 up to a quarter

@@ -59,6 +59,10 @@ public:
   const std::vector<float>& debug_iteration_ms() { finish_pending(); return iter_ms_; }
   // which schedule the last streaming frame ran: {samples per ray and iteration, ray parts, 1 = survivors numbered inside the evaluation kernel, 1 = decoupled loop}
   const int* debug_schedule() { finish_pending(); return last_schedule_; }
+  // the compose kernels of the streaming loops keep the transfer function's two tables in LDS while the pair fits this many bytes
+  // (16 per colour, 4 per opacity) and read them from global memory above it; whether the last frame's pair did
+  static constexpr size_t kTfnLdsBytes = 24 * 1024;
+  bool tfn_in_lds() { finish_pending(); return last_tfn_in_lds_; }
   // rank `part` of `parts` renders the pixel blocks b with b % parts == part (block = `block` consecutive pixels)
   void set_pixel_interleave(uint32_t block, uint32_t parts, uint32_t part)
   {
@@ -200,6 +204,7 @@ private:
   FrameStats stats_, completed_stats_;
   std::vector<float> iter_ms_;
   int last_schedule_[4] = {0, 0, 0, 0};
+  bool last_tfn_in_lds_ = false;
 };
 
 // diagnostics: the numbering of a march's survivors (pack_rays.h) as the kernel of its own, on host arrays: counts[ceil(n_in / 64)] as the

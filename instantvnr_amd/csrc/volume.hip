@@ -160,12 +160,19 @@ __global__ void update_macrocell_implicit_grouped_kernel(uint64_t n, vec3i dims,
   }
 }
 
-// macrocell.cu:153-193 (TFN alphas staged in LDS; any block size)
+// macrocell.cu:153-193 (any block size).  The opacity table is staged in LDS while it fits kMaxOpacityLdsBytes and read from global
+// memory above that: the same comparisons on the same operands either way, so the LDS a launch asks for does not grow with the table
+// (a table of more than 16 384 entries would ask for more than 64 KB, one of more than 40 960 for more than a compute unit has).
+constexpr size_t kMaxOpacityLdsBytes = 32 * 1024;
+
 __global__ void macrocell_max_opacity_kernel(uint32_t n_cells, DeviceTfn tfn, const float* __restrict__ range, float* __restrict__ out)
 {
   extern __shared__ float s_alphas[];
-  for (int j = threadIdx.x; j < tfn.n_alphas; j += blockDim.x) s_alphas[j] = tfn.alphas[j];
-  __syncthreads();
+  const bool staged = (size_t)tfn.n_alphas * sizeof(float) <= kMaxOpacityLdsBytes;   // uniform
+  if (staged) {
+    for (int j = threadIdx.x; j < tfn.n_alphas; j += blockDim.x) s_alphas[j] = tfn.alphas[j];
+    __syncthreads();
+  }
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_cells) return;
   const float rx = range[2 * (size_t)i] + 1.0f, ry = range[2 * (size_t)i + 1] - 1.0f;
@@ -178,7 +185,8 @@ __global__ void macrocell_max_opacity_kernel(uint32_t n_cells, DeviceTfn tfn, co
   if (il > (uint32_t)(len - 1)) il = (uint32_t)(len - 1);
   if (iu > (uint32_t)(len - 1)) iu = (uint32_t)(len - 1);
   float op = 0.0f;
-  for (uint32_t j = il; j <= iu; ++j) op = fmaxf(op, s_alphas[j]);
+  if (staged) { for (uint32_t j = il; j <= iu; ++j) op = fmaxf(op, s_alphas[j]); }
+  else { for (uint32_t j = il; j <= iu; ++j) op = fmaxf(op, tfn.alphas[j]); }
   out[i] = op;
 }
 
@@ -223,7 +231,8 @@ void MacroCell::update_max_opacity(const DeviceTfn& tfn, hipStream_t s)
 {
   if (tfn.n_alphas <= 0 || !allocated()) return;  // macrocell.cu:245
   const uint32_t n = (uint32_t)n_cells();
-  macrocell_max_opacity_kernel<<<div_round_up(n, 256), 256, (size_t)tfn.n_alphas * sizeof(float), s>>>(n, tfn, d_value_range(), d_max_opacity());
+  const size_t table_bytes = (size_t)tfn.n_alphas * sizeof(float);
+  macrocell_max_opacity_kernel<<<div_round_up(n, 256), 256, table_bytes <= kMaxOpacityLdsBytes ? table_bytes : 0, s>>>(n, tfn, d_value_range(), d_max_opacity());
   VNR_HIP_CHECK(hipGetLastError());
 }
 

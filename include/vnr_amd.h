@@ -464,6 +464,41 @@ typedef struct vnrAmdCorrectionBudget { double eps; uint64_t bytes; double eps_t
 vnrAmdCorrection vnrAmdNeuralVolumeBuildCorrectionWithinBytes(vnrAmdVolume neural, const void* d_ref, int value_type,
     const int64_t strides[3], float range_lo, float range_hi, uint64_t max_bytes, int form, double eps_hi, int rounds,
     void* stream, vnrAmdCorrectionBudget* report);
+/* AMD extension: corrections built straight into bit planes.  BuildCorrectionPacked is BuildCorrection (arguments, validation,
+ * refusals and messages, the refusal of a code wider than 32 bits included; a refused call returns NULL and keeps nothing
+ * resident) and gives the SAME correction: Serialize and SerializePacked bytes, every field of GetInfo, the corrected decode of
+ * the grid and of any box, and GetResidency in either form are bit for bit what BuildCorrection of the same arguments gives.
+ * What differs is how it gets there.  The correction is returned in the PACKED resident form (the packed payload as serialised,
+ * 16 bytes per macrocell, 4 bytes per group); no fixed-width payload is allocated on the device or the host, and no code crosses
+ * to the host during the call:
+ *   pass 1   chunks of whole groups of 64 codes over ALL cells of the grid, in the packed form's order (CorrectionRates' walk and
+ *            chunking), the network evaluated once; one wavefront takes one group, forms dec, r, q and z as BuildCorrection does,
+ *            stores the group's nbits in one byte per group of the grid, folds {max |q|, sum of nbits} per cell with integer
+ *            atomics, and reduces both error reports: before max |dec - ref|, after max |corrected - ref| with its first voxel by
+ *            lowest x-fastest index, the voxels with q != 0 and the NaN voxels.  (A cell that ends up not flagged has q == 0
+ *            everywhere, so its corrected value is dec.)  Kind 2 records nbits of ref's bit patterns whether or not a group differs;
+ *            a cell is flagged by "differs".
+ *   host     the per-cell pairs alone (8 bytes per macrocell): the width rule, the refusal, the entries {cell, width}, and the
+ *            exclusive sums that give each flagged cell's first group and first plane word.
+ *   index    one wavefront per flagged cell copies the cell's nbits into the packed group table, scans them into the per-group
+ *            index {first word inside the cell, nbits} and counts the groups with nbits > 0; a device prefix sum of the counts
+ *            orders the list of those groups (never an atomic).
+ *   pass 2   the network a second time for the listed groups alone, in chunks of the list: z again, one ballot per plane, lane b
+ *            keeps plane b, one 8-byte store per lane.  Its cost follows what is stored, not the grid.
+ * Scratch beyond the chunk scratch every round-trip call shares: 8 bytes per macrocell, 1 byte per group of the grid, 8 bytes per
+ * listed group.  The result does not depend on VNR_AMD_DECODE_CHUNK.  GetInfo on such a correction moves nothing (the fixed-width
+ * sizes follow from the entries); the first SerializePacked downloads table plus planes once and caches them; Serialize unpacks
+ * on the host from that; SetResidentForm(FIXED) unpacks on the device.  BuildCorrectionWithinBytes is unchanged.
+ *
+ * SerializePackedToDevice writes the exact "VNRCORP1" bytes of SerializePacked into device memory, for GPU-aware I/O or MPI: header
+ * and entries from the host, group table and planes device to device when the planes are resident (in PACKED form they are made
+ * resident first; in FIXED form the device pack runs as for SerializePacked).  *size is always set; d_bytes == NULL only reports
+ * it.  d_bytes follows d_out's pointer rules (allocation room is checked where the runtime knows the allocation); stream is the
+ * consumer's, waited for as DecodeToDevice does; the call returns after the bytes are there.
+ * Errors: a null handle or size; capacity < *size (both are named, nothing is written). */
+vnrAmdCorrection vnrAmdNeuralVolumeBuildCorrectionPacked(vnrAmdVolume neural, const void* d_ref, int value_type, const int64_t strides[3],
+                                                         float range_lo, float range_hi, double eps, void* stream);
+int  vnrAmdCorrectionSerializePackedToDevice(vnrAmdCorrection, void* d_bytes, size_t capacity, size_t* size, void* stream);
 /* hash-grid encode only (tcnn_impl_decoder.cu:177-230, column = level*F + f): fp16 [n][padded_width] */
 int    vnrAmdNeuralVolumeEncode(vnrAmdVolume, size_t n, const float* d_coords, uint16_t* d_features, void* stream);
 /* AMD extension: state of the brick image, the de-hashed inference copy of the hashed levels (csrc/network.h).  It is built

@@ -287,6 +287,8 @@ def lib():
     sig("vnrAmdReleaseCorrection", None, P)
     sig("vnrAmdNeuralVolumeCorrectionRates", I, P, P, I, I64P, F, F, C.POINTER(D), I, P, C.POINTER(CorrectionRate))
     sig("vnrAmdNeuralVolumeBuildCorrectionWithinBytes", P, P, P, I, I64P, F, F, U64, I, D, I, P, C.POINTER(CorrectionBudget))
+    sig("vnrAmdNeuralVolumeBuildCorrectionPacked", P, P, P, I, I64P, F, F, D, P)
+    sig("vnrAmdCorrectionSerializePackedToDevice", I, P, P, SZ, C.POINTER(SZ), P)
     _lib = L
     return L
 

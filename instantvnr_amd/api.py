@@ -552,6 +552,23 @@ class Correction(_Handle):
         b = bytes(b)
         return cls(lib().vnrAmdCreateCorrectionFromPackedBytes(b, len(b)))
 
+    def to_packed_device(self, d_ptr=None, stream=None):
+        """to_packed_bytes() written into device memory (include/vnr_amd.h, "corrections built straight into bit planes"), table and
+        planes device to device when they are resident.  d_ptr None -> the size in bytes; a DeviceArray (its whole size is the
+        capacity) or (address, capacity) -> the bytes written"""
+        n = C.c_size_t()
+        if d_ptr is None:
+            check(lib().vnrAmdCorrectionSerializePackedToDevice(self.h, None, 0, C.byref(n), None))
+            return n.value
+        if isinstance(d_ptr, DeviceArray):
+            ptr, capacity = d_ptr.ptr, d_ptr.nbytes
+        else:
+            ptr, capacity = d_ptr
+        if not ptr:
+            raise VnrAmdError("null device data")
+        check(lib().vnrAmdCorrectionSerializePackedToDevice(self.h, C.c_void_p(ptr), int(capacity), C.byref(n), C.c_void_p(stream) if stream else None))
+        return n.value
+
     RESIDENT_FORMS = {"fixed": 0, "packed": 1}
 
     def set_resident_form(self, form):
@@ -576,6 +593,14 @@ def vnrNeuralVolumeBuildCorrection(v, d_ref, dtype, eps, strides=None, value_ran
     p, _, t, s, _, _, st = _device_source_args(d_ref, dtype, strides, None, stream)
     lo, hi = _round_trip_range(np.dtype(dtype), value_range)
     return Correction(lib().vnrAmdNeuralVolumeBuildCorrection(v.h, p, t, s, lo, hi, float(eps), st))
+
+
+def vnrNeuralVolumeBuildCorrectionPacked(v, d_ref, dtype, eps, strides=None, value_range=None, stream=None):
+    """vnrNeuralVolumeBuildCorrection built straight into the packed resident form on the device: the same Correction, bit for bit in
+    everything it reports, stores and serialises, without a fixed-width payload anywhere and without a code crossing to the host"""
+    p, _, t, s, _, _, st = _device_source_args(d_ref, dtype, strides, None, stream)
+    lo, hi = _round_trip_range(np.dtype(dtype), value_range)
+    return Correction(lib().vnrAmdNeuralVolumeBuildCorrectionPacked(v.h, p, t, s, lo, hi, float(eps), st))
 
 
 def vnrNeuralVolumeCorrectionRates(v, d_ref, dtype, tolerances, strides=None, value_range=None, stream=None):

@@ -603,6 +603,22 @@ vnrAmdCorrection vnrAmdNeuralVolumeBuildCorrection(vnrAmdVolume v, const void* d
     return new vnrAmdCorrection_t{as_neural(v)->build_correction(DeviceSource{d_ref, value_type, strides, (hipStream_t)stream}, range_lo, range_hi, eps)};
   });
 }
+vnrAmdCorrection vnrAmdNeuralVolumeBuildCorrectionPacked(vnrAmdVolume v, const void* d_ref, int value_type, const int64_t strides[3], float range_lo, float range_hi,
+                                                         double eps, void* stream)
+{
+  return guarded_new<vnrAmdCorrection_t>([&]() {
+    return new vnrAmdCorrection_t{as_neural(v)->build_correction_packed(DeviceSource{d_ref, value_type, strides, (hipStream_t)stream}, range_lo, range_hi, eps)};
+  });
+}
+int vnrAmdCorrectionSerializePackedToDevice(vnrAmdCorrection c, void* d_bytes, size_t capacity, size_t* size, void* stream)
+{
+  return guarded([&]() {
+    Correction* k = as_correction(c);
+    if (!size) throw std::runtime_error("null result");
+    if (!Runtime::get().ready() && (d_bytes || (!k->data.cells.empty() && !k->has_packed))) Runtime::get().init(-1);
+    correction_serialize_packed_to_device(*k, d_bytes, capacity, size, (hipStream_t)stream);
+  });
+}
 int vnrAmdNeuralVolumeCorrectionRates(vnrAmdVolume v, const void* d_ref, int value_type, const int64_t strides[3], float range_lo, float range_hi,
                                       const double* eps, int n_eps, void* stream, vnrAmdCorrectionRate* out)
 {
@@ -654,13 +670,15 @@ int vnrAmdCorrectionGetInfo(vnrAmdCorrection c, vnrAmdCorrectionInfo* out)
   return guarded([&]() {
     Correction* k = as_correction(c);
     if (!out) throw std::runtime_error("null result");
-    k->host_payload();   // (a correction read from packed bytes: its fixed-width sizes)
+    if (!k->direct) k->host_payload();   // (a correction read from packed bytes: its fixed-width sizes)
     const CorrectionHeader& h = k->data.h;
+    // a direct build moves nothing for this: the fixed-width payload's size follows from the entries
+    const uint64_t payload_bytes = k->direct ? correction_fixed_payload_bytes(h, k->data.cells) : k->data.payload.size();
     *out = vnrAmdCorrectionInfo{};
     for (int a = 0; a < 3; ++a) { out->dims[a] = h.dims[a]; out->worst_after[a] = k->worst_after[a]; }
     out->value_type = h.value_type; out->kind = (int)h.kind; out->eps = h.eps; out->range_lo = h.range_lo; out->range_hi = h.range_hi;
     out->n_cells = correction_n_cells(h.dims); out->n_flagged = k->data.cells.size(); out->n_voxels_flagged = k->n_voxels_flagged;
-    out->payload_bytes = k->data.payload.size(); out->serialized_bytes = correction_serialized_bytes(k->data); out->n_nan = k->n_nan;
+    out->payload_bytes = payload_bytes; out->serialized_bytes = kCorrectionHeaderBytes + 8 * k->data.cells.size() + payload_bytes; out->n_nan = k->n_nan;
     out->params_hash = h.params_hash; out->n_params = h.n_params; out->max_abs_before = k->max_abs_before; out->max_abs_after = h.max_abs_after;
   });
 }
@@ -669,6 +687,7 @@ int vnrAmdCorrectionSerialize(vnrAmdCorrection c, void** bytes, size_t* size)
   return guarded([&]() {
     Correction* k = as_correction(c);
     if (!bytes || !size) throw std::runtime_error("null result");
+    if (k->direct && !k->has_packed) correction_packed_payload(*k, Runtime::get().stream);   // a direct build: table and planes, downloaded once
     k->host_payload();
     const std::vector<uint8_t> b = correction_write(k->data);
     *bytes = dup_bytes(b.data(), b.size());

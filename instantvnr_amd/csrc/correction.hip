@@ -12,9 +12,16 @@
 // correction_rates ("corrections to a byte budget") answers what many tolerances would cost without building any: one chunked
 // evaluation in the packed form's order, a wave per group of 64 codes, the build's quantise per tolerance, wave reductions and
 // integer atomics per cell; tests/correction_rate_ref.py restates it.  The search on top of it is correction_budget.cpp, host only.
+//
+// build_correction_packed ("corrections built straight into bit planes", at the end of this file) gives build_correction's correction
+// in the packed resident form without the fixed-width codes in between: the rate pass's walk for one tolerance with the error reports
+// taken from it, n_cells pairs through the host (correction_direct.cpp), an index kernel, and the planes of the groups that store any
+// from a second evaluation of those groups alone.  correction_serialize_packed_to_device writes the packed bytes into device memory.
 #include "box_walk.h"
+#include "correction_direct.h"
 
 #include <cstdio>
+#include <cstring>
 
 namespace vnr {
 
@@ -470,16 +477,29 @@ struct GroupWalk {
 
 // the voxel centres of the groups [g0, g0 + n / 64) in that order: decode_coords_kernel's arithmetic.  A lane beyond its cell's voxels
 // (the last group of a ragged cell) gets the cell's last voxel: its value is evaluated and never read.
-__global__ void __launch_bounds__(kBlock) correction_rate_coords_kernel(GroupWalk w, uint64_t g0, uint32_t n, vec3f rdims, float* __restrict__ coords)
+__device__ __forceinline__ void group_lane_coords(const GroupWalk& w, uint64_t gid, uint32_t t, vec3f rdims, float* __restrict__ coords)
 {
-  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
-  if (t >= n) return;
-  const GroupWalk::Place p = w.place(g0 + (t >> 6));
+  const GroupWalk::Place p = w.place(gid);
   const uint32_t li = std::min(p.group * 64u + (t & 63u), p.voxels - 1u);
   const uint32_t row = li / p.cx, lx = li - row * p.cx, lz = row / p.cy, ly = row - lz * p.cy;
   coords[3 * (size_t)t + 0] = ((float)(int)(p.x0 + lx) + 0.5f) * rdims.x;
   coords[3 * (size_t)t + 1] = ((float)(int)(p.y0 + ly) + 0.5f) * rdims.y;
   coords[3 * (size_t)t + 2] = ((float)(int)(p.z0 + lz) + 0.5f) * rdims.z;
+}
+
+__global__ void __launch_bounds__(kBlock) correction_rate_coords_kernel(GroupWalk w, uint64_t g0, uint32_t n, vec3f rdims, float* __restrict__ coords)
+{
+  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= n) return;
+  group_lane_coords(w, g0 + (t >> 6), t, rdims, coords);
+}
+
+// the same for a list of groups (the direct build's pass 2): group t / 64 of the chunk is list[t / 64] of the walk
+__global__ void __launch_bounds__(kBlock) correction_list_coords_kernel(GroupWalk w, const uint64_t* __restrict__ list, uint32_t n, vec3f rdims, float* __restrict__ coords)
+{
+  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= n) return;
+  group_lane_coords(w, list[t >> 6], t, rdims, coords);
 }
 
 struct RateBatch {
@@ -953,6 +973,349 @@ void NeuralVolume::decode_to_device_corrected(Correction& corr, const DeviceTarg
     VNR_HIP_CHECK(hipGetLastError());
   }
   VNR_HIP_CHECK(hipStreamSynchronize(stream));   // on return the box is there
+}
+
+// ---- the direct build: field and network -> resident planes plus index, no fixed-width code in between ----------------------------------------
+// (include/vnr_amd.h, "corrections built straight into bit planes").  Pass 1 is the rate pass for one tolerance with more taken from
+// it: a group's nbits into one byte per group of the GRID, the per-cell pair, and both error reports -- in a cell that ends up not
+// flagged every q is 0 and corrected_value(dec, 0) is dec (kind 2: dec has ref's bits), so the error after needs no cell table.  The
+// host sees n_cells pairs (correction_direct.cpp).  The index kernel copies the flagged cells' nbits into the packed group table,
+// scans them into d_plane_groups and counts the cell's groups that store planes; the scan of guided_sampler.hip turns the counts into
+// each cell's place in the list of those groups, so the list is in the walk's order whatever order the waves ran in.  Pass 2 evaluates
+// the listed groups alone and stores their planes, lane b plane b, as correction_pack.hip does.
+namespace {
+
+static_assert(sizeof(CorrectionDirectStat) == sizeof(RateCell), "the per-cell pair goes to correction_direct_plan as it is");
+
+struct DirectCell { uint64_t grid_group0; uint32_t group0, groups; };   // a flagged cell: its first group in the walk, in the packed table; its groups
+
+// a lane's voxel of a group: ref through the strides, the decoded value, the x-fastest index in the grid
+template <typename T>
+struct GroupLane {
+  bool has;   // the pack fills the other lanes with codes of value 0
+  T rv, dec;
+  uint64_t index;
+};
+
+template <typename T>
+__device__ __forceinline__ GroupLane<T> load_group_lane(const T* __restrict__ ref, int64_t sx, int64_t sy, int64_t sz, const GroupWalk& w, const GroupWalk::Place& p,
+                                                        uint32_t lane, const float* __restrict__ value, const Conversion& c)
+{
+  GroupLane<T> v{false, T(0), T(0), 0};
+  const uint32_t li = p.group * 64u + lane;
+  v.has = li < p.voxels;
+  if (v.has) {
+    const uint32_t row = li / p.cx, lx = li - row * p.cx, lz = row / p.cy, ly = row - lz * p.cy;
+    const uint32_t x = p.x0 + lx, y = p.y0 + ly, z = p.z0 + lz;
+    v.rv = ref[(int64_t)x * sx + (int64_t)y * sy + (int64_t)z * sz];
+    v.dec = convert_value<T>(*value, c);
+    v.index = x + (uint64_t)w.dx * (y + (uint64_t)w.dy * z);
+  }
+  return v;
+}
+
+// the build's code of a voxel and its unsigned z of the packed form
+template <typename T>
+__device__ __forceinline__ uint64_t code_z(T dec, T rv, const Quantiser& k, int64_t& q, uint32_t& aq, bool& nan)
+{
+  quantise<T>(dec, rv, k, q, aq, nan);
+  if constexpr (std::is_floating_point_v<T>) {
+    if (k.kind == kCorrectionVerbatim) return (uint64_t)bits_of(rv);
+  }
+  return ((uint64_t)q << 1) ^ (uint64_t)(q >> 63);
+}
+
+// greater, or equal with the lower index (a NaN never wins): a lane meets its groups in no order of the grid index
+__device__ __forceinline__ void take_worst(double& mx, uint64_t& mi, double a, uint64_t i)
+{
+  if (a > mx || (a == mx && i < mi)) { mx = a; mi = i; }
+}
+
+// pass 1.  groups [g0, g0 + n_groups) of the walk, values as in correction_rate_kernel.  group_nbits[group of the grid] gets every
+// group's nbits (kind 2: of ref's bit patterns, whether or not the group differs); the cell's pair is folded as the rate kernel folds
+// it; before / after: a partial per block, a = voxels with q != 0, b = NaN voxels (before only).
+template <typename T>
+__global__ void __launch_bounds__(kBlock) correction_direct_measure_kernel(const T* __restrict__ ref, int64_t sx, int64_t sy, int64_t sz, GroupWalk w, uint64_t g0,
+                                                                           uint32_t n_groups, const float* __restrict__ values, Conversion c, Quantiser k,
+                                                                           RateCell* __restrict__ stats, uint8_t* __restrict__ group_nbits,
+                                                                           Partial* __restrict__ before, Partial* __restrict__ after)
+{
+  const uint32_t lane = threadIdx.x & 63u, waves = kBlock / 64;
+  double bmx = -1.0, amx = -1.0;
+  uint64_t bmi = ~0ull, ami = ~0ull, n_over = 0, n_nan = 0;
+  for (uint32_t g = blockIdx.x * waves + (threadIdx.x >> 6); g < n_groups; g += gridDim.x * waves) {
+    const GroupWalk::Place p = w.place(g0 + g);
+    const GroupLane<T> v = load_group_lane<T>(ref, sx, sy, sz, w, p, lane, values + ((size_t)g * 64 + lane), c);
+    int64_t q = 0; uint32_t aq = 0; bool nan = false;
+    uint64_t z = 0;
+    if (v.has) {
+      z = code_z<T>(v.dec, v.rv, k, q, aq, nan);
+      take_worst(bmx, bmi, fabs((double)v.dec - (double)v.rv), v.index);
+      T out = corrected_value<T>(v.dec, q, k);
+      if constexpr (std::is_floating_point_v<T>) {
+        if (k.kind == kCorrectionVerbatim) out = v.rv;
+      }
+      take_worst(amx, ami, fabs((double)out - (double)v.rv), v.index);
+      n_over += aq ? 1 : 0;
+      n_nan += nan ? 1 : 0;
+    }
+    const uint64_t differ = __ballot(q != 0);
+    const uint32_t nbits = wave_max(z ? 64u - (uint32_t)__clzll((long long)z) : 0u);
+    const uint32_t m = wave_max(aq);
+    if (lane == 0) {
+      group_nbits[g0 + g] = (uint8_t)nbits;
+      if (differ != 0 || k.kind == kCorrectionVerbatim) {
+        RateCell* s = stats + p.cell;
+        if (m) atomicMax(&s->max_q, m);
+        if (nbits) atomicAdd(&s->nbits, nbits);
+      }
+    }
+  }
+  block_reduce(bmx, bmi, n_over, n_nan);
+  if (threadIdx.x == 0) merge_partial<uint64_t>(before, bmx, bmi, n_over, n_nan);
+  __syncthreads();   // (block_reduce's LDS is read by thread 0 until here)
+  uint64_t na = 0, nb = 0;
+  block_reduce(amx, ami, na, nb);
+  if (threadIdx.x == 0) merge_partial<uint64_t>(after, amx, ami, 0, 0);
+}
+
+// exclusive prefix sum over the lanes of a wave
+__device__ __forceinline__ uint32_t wave_exclusive_sum(uint32_t v, uint32_t lane)
+{
+  uint32_t incl = v;
+  for (int off = 1; off < 64; off <<= 1) {
+    const uint32_t t = __shfl_up(incl, off, 64);
+    if (lane >= (uint32_t)off) incl += t;
+  }
+  return incl - v;
+}
+
+// the index: a block is one wave and takes flagged cells by block stride, lane g the cell's group g (a cell has at most 64)
+__global__ void __launch_bounds__(64) correction_direct_index_kernel(const DirectCell* __restrict__ cells, uint32_t n_cells, const uint8_t* __restrict__ group_nbits,
+                                                                     uint8_t* __restrict__ table, uint32_t* __restrict__ plane_groups, uint64_t* __restrict__ stored)
+{
+  const uint32_t lane = threadIdx.x;
+  for (uint64_t c = blockIdx.x; c < n_cells; c += gridDim.x) {
+    const DirectCell dc = cells[c];
+    const uint32_t nbits = lane < dc.groups ? group_nbits[dc.grid_group0 + lane] : 0u;
+    const uint32_t first = wave_exclusive_sum(nbits, lane);   // at most 63 * 64
+    if (lane < dc.groups) {
+      table[dc.group0 + lane] = (uint8_t)nbits;
+      plane_groups[dc.group0 + lane] = first | nbits << 16;
+    }
+    const uint64_t with_planes = __ballot(nbits != 0);
+    if (lane == 0) stored[c] = (uint64_t)__popcll(with_planes);
+  }
+}
+
+// stored: now the inclusive sums of the cells' counts.  The cell's groups that store planes go to the list, in their order
+__global__ void __launch_bounds__(64) correction_direct_list_kernel(const DirectCell* __restrict__ cells, uint32_t n_cells, const uint32_t* __restrict__ plane_groups,
+                                                                    const uint64_t* __restrict__ stored, uint64_t* __restrict__ list)
+{
+  const uint32_t lane = threadIdx.x;
+  for (uint64_t c = blockIdx.x; c < n_cells; c += gridDim.x) {
+    const DirectCell dc = cells[c];
+    const uint32_t nbits = lane < dc.groups ? plane_groups[dc.group0 + lane] >> 16 : 0u;
+    const uint64_t with_planes = __ballot(nbits != 0);
+    const uint64_t first = stored[c] - (uint64_t)__popcll(with_planes);
+    if (nbits) list[first + (uint64_t)__popcll(with_planes & ((1ull << lane) - 1ull))] = dc.grid_group0 + lane;
+  }
+}
+
+// pass 2.  groups list[0 .. n_groups) of the walk, all of flagged cells and with nbits > 0, values[64 * g + lane]: z again, one ballot
+// per plane, lane b keeps plane b, one 8-byte store per lane at the cell's first word + the group's
+template <typename T>
+__global__ void __launch_bounds__(kBlock) correction_direct_planes_kernel(const T* __restrict__ ref, int64_t sx, int64_t sy, int64_t sz, GroupWalk w,
+                                                                          const uint64_t* __restrict__ list, uint32_t n_groups, const float* __restrict__ values,
+                                                                          Conversion c, Quantiser k, const Correction::PlaneCell* __restrict__ cells,
+                                                                          const uint32_t* __restrict__ plane_groups, uint64_t* __restrict__ planes)
+{
+  const uint32_t lane = threadIdx.x & 63u, waves = kBlock / 64;
+  for (uint32_t g = blockIdx.x * waves + (threadIdx.x >> 6); g < n_groups; g += gridDim.x * waves) {
+    const GroupWalk::Place p = w.place(list[g]);
+    const GroupLane<T> v = load_group_lane<T>(ref, sx, sy, sz, w, p, lane, values + ((size_t)g * 64 + lane), c);
+    int64_t q; uint32_t aq; bool nan;
+    const uint64_t z = v.has ? code_z<T>(v.dec, v.rv, k, q, aq, nan) : 0ull;   // a lane beyond its cell's voxels contributes 0
+    const Correction::PlaneCell pc = cells[p.cell];
+    const uint32_t gi = (uint32_t)__builtin_amdgcn_readfirstlane((int)plane_groups[pc.group0 + p.group]);
+    const uint32_t nb = std::min(gi >> 16, 64u);
+    uint64_t keep = 0;
+    for (uint32_t b = 0; b < nb; ++b) {
+      const uint64_t plane = __ballot((int)((z >> b) & 1));
+      if (lane == b) keep = plane;
+    }
+    if (lane < nb) planes[pc.word0 + (gi & 0xffffu) + lane] = keep;
+  }
+}
+
+}  // namespace
+
+std::shared_ptr<Correction> NeuralVolume::build_correction_packed(const DeviceSource& ref, float range_lo, float range_hi, double eps)
+{
+  if (!net_.valid()) throw std::runtime_error("neural volume has no valid network");
+  if (!(eps >= 0.0) || !std::isfinite(eps)) throw std::runtime_error("eps must be a finite tolerance >= 0 in data units, got " + std::to_string(eps));
+  const vec3i grid = desc.dims;
+  vec3i lower;
+  const BoxLayout L = validate_box_array(ref.data, ref.type, ref.strides, nullptr, nullptr, grid, lower, range_lo, range_hi);
+  const int64_t sx = ref.strides ? ref.strides[0] : 1, sy = ref.strides ? ref.strides[1] : (int64_t)L.bx, sz = ref.strides ? ref.strides[2] : (int64_t)(L.bx * L.by);
+  const vec3f rdims = {1.0f / (float)grid.x, 1.0f / (float)grid.y, 1.0f / (float)grid.z};
+  const Conversion c{range_lo, range_hi - range_lo, range_lo < range_hi};
+  const bool is_float = correction_type_is_float(ref.type);
+  const uint32_t kind = !is_float ? kCorrectionInteger : (eps > 0.0 ? kCorrectionFloat : kCorrectionVerbatim);
+  const Quantiser k = make_quantiser(kind, eps);
+  const GroupWalk w = make_group_walk(grid);
+  const int dims[3] = {grid.x, grid.y, grid.z};
+  const uint64_t n_cells = correction_n_cells(dims);
+  const uint64_t chunk_groups = std::min(std::max<uint64_t>(1, chunk_samples() / 64), w.n_groups);   // whole groups, as the rate pass
+
+  auto corr = std::make_shared<Correction>();
+  CorrectionHeader& h = corr->data.h;
+  h.value_type = ref.type;
+  for (int a = 0; a < 3; ++a) h.dims[a] = dims[a];
+  h.eps = eps; h.range_lo = range_lo; h.range_hi = range_hi; h.kind = kind;
+  h.step = correction_step(kind, eps);
+  h.n_params = net_.n_params();
+  h.params_hash = params_hash();
+
+  const uint32_t max_blocks = (uint32_t)Runtime::get().n_cus * 8;
+  dd_coords_.ensure(3 * 64 * chunk_groups);
+  dd_values_.ensure(64 * chunk_groups);
+  dd_partials_.ensure((size_t)2 * (max_blocks + 1) * (sizeof(Partial) / sizeof(double)));
+  Partial* before_partials = (Partial*)dd_partials_.ptr;
+  Partial* after_partials = before_partials + (max_blocks + 1);
+  DeviceBuffer<RateCell> stats(MemTag::Network);
+  DeviceBuffer<uint8_t> group_nbits(MemTag::Network);
+  stats.resize(n_cells);
+  group_nbits.resize(w.n_groups);   // (every byte is written by pass 1)
+  EventGuard ev;
+  wait_for(ref.producer, stream, ev);
+
+  // pass 1
+  worst_init_kernel<<<div_round_up(2 * (max_blocks + 1), kBlock), kBlock, 0, stream>>>(before_partials, 2 * (max_blocks + 1));
+  VNR_HIP_CHECK(hipGetLastError());
+  stats.zero(stream);
+  for (uint64_t g0 = 0; g0 < w.n_groups; g0 += chunk_groups) {
+    const uint32_t n_groups = (uint32_t)std::min(chunk_groups, w.n_groups - g0), n = 64 * n_groups;
+    correction_rate_coords_kernel<<<div_round_up(n, kBlock), kBlock, 0, stream>>>(w, g0, n, rdims, dd_coords_.ptr);
+    VNR_HIP_CHECK(hipGetLastError());
+    net_.inference(dd_coords_.ptr, dd_values_.ptr, n, nullptr, n, stream);
+    const uint32_t blocks = std::max(1u, std::min(div_round_up(n_groups, kBlock / 64), max_blocks));
+    dispatch_type(ref.type, [&](auto* tag) {
+      using T = std::remove_pointer_t<decltype(tag)>;
+      correction_direct_measure_kernel<T><<<blocks, kBlock, 0, stream>>>((const T*)ref.data, sx, sy, sz, w, g0, n_groups, dd_values_.ptr, c, k, stats.ptr,
+                                                                         group_nbits.ptr, before_partials, after_partials);
+    });
+    VNR_HIP_CHECK(hipGetLastError());
+  }
+  worst_final_kernel<<<1, kBlock, 0, stream>>>(before_partials, max_blocks, before_partials + max_blocks);
+  VNR_HIP_CHECK(hipGetLastError());
+  worst_final_kernel<<<1, kBlock, 0, stream>>>(after_partials, max_blocks, after_partials + max_blocks);
+  VNR_HIP_CHECK(hipGetLastError());
+  Partial before, after;
+  std::vector<CorrectionDirectStat> cells(n_cells);
+  VNR_HIP_CHECK(hipMemcpyAsync(&before, before_partials + max_blocks, sizeof(before), hipMemcpyDeviceToHost, stream));
+  VNR_HIP_CHECK(hipMemcpyAsync(&after, after_partials + max_blocks, sizeof(after), hipMemcpyDeviceToHost, stream));
+  VNR_HIP_CHECK(hipMemcpyAsync(cells.data(), stats.ptr, n_cells * sizeof(RateCell), hipMemcpyDeviceToHost, stream));
+  VNR_HIP_CHECK(hipStreamSynchronize(stream));
+
+  // the host: n_cells pairs in, the entries and the flagged cells' places out
+  const CorrectionDirectPlan plan = correction_direct_plan(dims, kind, (uint32_t)device_value_type_size(ref.type), cells.data(), n_cells);
+  if (plan.refused)
+    throw std::runtime_error("the tolerance needs codes wider than 32 bits: eps " + std::to_string(eps) + " against a maximum error of " + std::to_string(before.max_abs));
+  if (plan.n_groups > 0xffffffffull) throw std::runtime_error("the correction has more than 2^32 groups");
+  corr->data.cells = plan.cells;
+  corr->n_voxels_flagged = before.a;
+  corr->n_nan = before.b;
+  corr->max_abs_before = before.max_abs < 0.0 ? std::numeric_limits<double>::quiet_NaN() : before.max_abs;
+  if (after.max_abs < 0.0) {   // every voxel's error is a NaN
+    h.max_abs_after = std::numeric_limits<double>::quiet_NaN();
+  } else {
+    h.max_abs_after = after.max_abs;
+    index_to_voxel(after.worst, L, corr->worst_after);
+  }
+  corr->resident_form = 1;
+  corr->direct = true;
+  if (plan.cells.empty()) {   // holds nothing, as every correction without a flagged cell
+    corr->has_packed = true;
+    return corr;
+  }
+
+  const uint32_t n_flagged = (uint32_t)plan.cells.size();
+  const uint64_t table_bytes = correction_group_table_bytes(plan.n_groups);
+  std::vector<Correction::PlaneCell> plane_cells(n_cells, Correction::PlaneCell{~0ull, 0, 0});
+  std::vector<DirectCell> direct_cells(n_flagged);
+  for (uint32_t i = 0; i < n_flagged; ++i) {
+    const CorrectionDirectPlace& at = plan.places[i];
+    plane_cells[plan.cells[i].cell] = Correction::PlaneCell{at.word0, (uint32_t)at.group0, 0};
+    direct_cells[i] = DirectCell{at.grid_group0, (uint32_t)at.group0, (uint32_t)correction_cell_groups(correction_cell_voxels(dims, plan.cells[i].cell))};
+  }
+  DeviceBuffer<DirectCell> d_cells(MemTag::Network);
+  DeviceBuffer<uint64_t> stored(MemTag::Network), scan_scratch(MemTag::Network), list(MemTag::Network);
+  d_cells.upload(direct_cells.data(), n_flagged, stream);
+  corr->d_plane_cells.upload(plane_cells.data(), n_cells, stream);
+  corr->d_plane_groups.resize(plan.n_groups);
+  corr->d_packed.resize(table_bytes + 8 * plan.n_words);
+  VNR_HIP_CHECK(hipMemsetAsync(corr->d_packed.ptr, 0, table_bytes, stream));   // (the table's padding)
+  stored.resize(n_flagged);
+  const uint32_t cell_blocks = std::min(n_flagged, 1u << 20);
+  correction_direct_index_kernel<<<cell_blocks, 64, 0, stream>>>(d_cells.ptr, n_flagged, group_nbits.ptr, corr->d_packed.ptr, corr->d_plane_groups.ptr, stored.ptr);
+  VNR_HIP_CHECK(hipGetLastError());
+  device_inclusive_scan(stored.ptr, n_flagged, scan_scratch, stream);
+  uint64_t n_stored = 0;   // groups with planes: one count, no code, crosses to the host
+  VNR_HIP_CHECK(hipMemcpyAsync(&n_stored, stored.ptr + (n_flagged - 1), sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+  VNR_HIP_CHECK(hipStreamSynchronize(stream));   // (the host vectors above are done with, too)
+  if (n_stored > plan.n_groups) throw std::runtime_error("internal error: more groups store planes than the flagged cells have");
+  if (n_stored) {
+    list.resize(n_stored);
+    correction_direct_list_kernel<<<cell_blocks, 64, 0, stream>>>(d_cells.ptr, n_flagged, corr->d_plane_groups.ptr, stored.ptr, list.ptr);
+    VNR_HIP_CHECK(hipGetLastError());
+    uint64_t* planes = reinterpret_cast<uint64_t*>(corr->d_packed.ptr + table_bytes);
+    // pass 2: the network a second time, for the groups that store planes alone
+    for (uint64_t l0 = 0; l0 < n_stored; l0 += chunk_groups) {
+      const uint32_t n_groups = (uint32_t)std::min(chunk_groups, n_stored - l0), n = 64 * n_groups;
+      correction_list_coords_kernel<<<div_round_up(n, kBlock), kBlock, 0, stream>>>(w, list.ptr + l0, n, rdims, dd_coords_.ptr);
+      VNR_HIP_CHECK(hipGetLastError());
+      net_.inference(dd_coords_.ptr, dd_values_.ptr, n, nullptr, n, stream);
+      const uint32_t blocks = std::max(1u, std::min(div_round_up(n_groups, kBlock / 64), max_blocks));
+      dispatch_type(ref.type, [&](auto* tag) {
+        using T = std::remove_pointer_t<decltype(tag)>;
+        correction_direct_planes_kernel<T><<<blocks, kBlock, 0, stream>>>((const T*)ref.data, sx, sy, sz, w, list.ptr + l0, n_groups, dd_values_.ptr, c, k,
+                                                                          corr->d_plane_cells.ptr, corr->d_plane_groups.ptr, planes);
+      });
+      VNR_HIP_CHECK(hipGetLastError());
+    }
+    VNR_HIP_CHECK(hipStreamSynchronize(stream));   // the scratch of this call goes out of scope
+  }
+  corr->planes_uploaded = true;
+  return corr;
+}
+
+void correction_serialize_packed_to_device(Correction& corr, void* d_bytes, size_t capacity, size_t* size, hipStream_t consumer)
+{
+  if (!size) throw std::runtime_error("null result");
+  const CorrectionData& d = corr.data;
+  hipStream_t stream = Runtime::get().stream;
+  uint64_t payload_bytes = 0;   // of the packed payload: the host copy's if there is one, else the resident planes'
+  if (!d.cells.empty()) {
+    if (!corr.has_packed && !corr.planes_uploaded) correction_packed_payload(corr, stream);   // the device pack, cached as by SerializePacked
+    payload_bytes = corr.has_packed ? corr.packed_payload.size() : corr.d_packed.bytes();
+  }
+  std::vector<uint8_t> head = correction_packed_write(d.h, d.cells, std::vector<uint8_t>());
+  std::memcpy(head.data() + 80, &payload_bytes, sizeof(uint64_t));   // payload_bytes of the header (correction_format.h)
+  *size = head.size() + payload_bytes;
+  if (!d_bytes) return;
+  if (capacity < *size)
+    throw std::runtime_error("capacity (" + std::to_string(capacity) + " bytes) is smaller than the packed correction (" + std::to_string(*size) + " bytes)");
+  require_room(d_bytes, *size, "the packed bytes");
+  if (payload_bytes && !corr.planes_uploaded && corr.resident_form == 1) correction_make_resident(corr, stream);   // PACKED: the planes, then device to device
+  EventGuard ev;
+  wait_for(consumer, stream, ev);   // what the destination held may still be being read
+  VNR_HIP_CHECK(hipMemcpyAsync(d_bytes, head.data(), head.size(), hipMemcpyHostToDevice, stream));
+  if (payload_bytes) {
+    if (corr.planes_uploaded) VNR_HIP_CHECK(hipMemcpyAsync((uint8_t*)d_bytes + head.size(), corr.d_packed.ptr, payload_bytes, hipMemcpyDeviceToDevice, stream));
+    else VNR_HIP_CHECK(hipMemcpyAsync((uint8_t*)d_bytes + head.size(), corr.packed_payload.data(), payload_bytes, hipMemcpyHostToDevice, stream));
+  }
+  VNR_HIP_CHECK(hipStreamSynchronize(stream));   // on return the bytes are there; `head` goes out of scope
 }
 
 }  // namespace vnr

@@ -162,6 +162,7 @@ uint32_t cell_blocks(size_t n_cells) { return (uint32_t)std::min<size_t>(n_cells
 void unpack_on_device(Correction& corr, hipStream_t stream)
 {
   const CorrectionData& d = corr.data;
+  if (!corr.has_packed) correction_packed_payload(corr, stream);   // (a direct build: the group table has not been on the host yet)
   const std::vector<PackCell> cells = make_pack_cells(d);
   const uint64_t table_bytes = correction_group_table_bytes(correction_n_groups(d.h, d.cells));
   // the cells' first plane words, from the table (validated when the bytes were read)
@@ -194,7 +195,7 @@ void unpack_on_device(Correction& corr, hipStream_t stream)
 void correction_ensure_device_payload(Correction& corr, hipStream_t stream)
 {
   if (corr.uploaded || corr.payload_uploaded || corr.data.cells.empty()) return;
-  if (corr.from_packed || corr.planes_uploaded) {
+  if (corr.from_packed || corr.direct || corr.planes_uploaded) {
     unpack_on_device(corr, stream);
   } else {
     corr.d_payload.upload(corr.data.payload.data(), corr.data.payload.size(), stream);
@@ -208,6 +209,13 @@ const std::vector<uint8_t>& correction_packed_payload(Correction& corr, hipStrea
   if (corr.has_packed) return corr.packed_payload;
   const CorrectionData& d = corr.data;
   if (d.cells.empty()) {   // no group, no plane
+    corr.has_packed = true;
+    return corr.packed_payload;
+  }
+  if (corr.direct) {   // built straight into the planes: table and planes as they lie on the device, downloaded once
+    if (!corr.planes_uploaded) throw std::runtime_error("internal error: a direct correction holds its planes neither on the host nor on the device");
+    corr.packed_payload.resize(corr.d_packed.count);
+    corr.d_packed.download(corr.packed_payload.data(), corr.d_packed.count, stream);   // (synchronises)
     corr.has_packed = true;
     return corr.packed_payload;
   }

@@ -194,6 +194,31 @@ bool staged_search_wanted()
 
 }  // namespace
 
+void device_inclusive_scan(uint64_t* d_data, uint64_t n, DeviceBuffer<uint64_t>& scratch, hipStream_t s)
+{
+  if (n == 0) return;
+  std::vector<uint64_t> counts{n};
+  while (counts.back() > 1) counts.push_back(blocks_of(counts.back()));
+  size_t words = 1;   // (a one-element scan still needs a place for its block sum)
+  for (size_t l = 1; l < counts.size(); ++l) words += counts[l];
+  scratch.ensure(words);
+  std::vector<uint64_t*> level{d_data};
+  {
+    uint64_t* p = scratch.ptr;
+    for (size_t l = 1; l < counts.size(); ++l) { level.push_back(p); p += counts[l]; }
+    if (counts.size() == 1) level.push_back(p);
+  }
+  for (size_t l = 0; l < std::max<size_t>(1, counts.size() - 1); ++l) {   // every level but the last one-element one scans itself
+    scan_sums_kernel<<<(uint32_t)blocks_of(counts[l]), kScanBlock, 0, s>>>(level[l], counts[l], level[l + 1]);
+    VNR_HIP_CHECK(hipGetLastError());
+  }
+  for (size_t l = counts.size(); l-- > 0;) {   // a level of one block is final as it stands
+    if (counts[l] <= (uint64_t)kScanBlock) continue;
+    scan_add_offsets_kernel<<<(uint32_t)(blocks_of(counts[l]) - 1), kScanBlock, 0, s>>>(level[l], counts[l], level[l + 1]);
+    VNR_HIP_CHECK(hipGetLastError());
+  }
+}
+
 void SimpleVolume::check_uniform_fraction(float uniform_fraction)
 {
   if (!(uniform_fraction >= 0.0f && uniform_fraction <= 1.0f))

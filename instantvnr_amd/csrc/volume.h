@@ -137,10 +137,14 @@ struct Correction {
   DeviceBuffer<PlaneCell> d_plane_cells{MemTag::Network};
   DeviceBuffer<uint32_t> d_plane_groups{MemTag::Network};   // word | nbits << 16
   bool planes_uploaded = false;
+  // Built straight into the planes (NeuralVolume::build_correction_packed): d_packed and the index came from the device, there is no
+  // fixed-width payload anywhere and packed_payload is empty until correction_packed_payload downloads d_packed (has_packed); from
+  // then on the correction behaves like one read from packed bytes.
+  bool direct = false;
   const uint64_t* d_planes() const { return reinterpret_cast<const uint64_t*>(d_packed.ptr + correction_group_table_bytes(d_plane_groups.count)); }
-  const std::vector<uint8_t>& host_payload()   // data.payload, unpacked on the host at its first use
+  const std::vector<uint8_t>& host_payload()   // data.payload, unpacked on the host at its first use (direct: has_packed comes first)
   {
-    if (from_packed && data.payload.empty() && !data.cells.empty()) data.payload = correction_unpack(data.h, data.cells, packed_payload);
+    if ((from_packed || (direct && has_packed)) && data.payload.empty() && !data.cells.empty()) data.payload = correction_unpack(data.h, data.cells, packed_payload);
     return data.payload;
   }
 };
@@ -155,6 +159,13 @@ const std::vector<uint8_t>& correction_packed_payload(Correction& corr, hipStrea
 void correction_make_resident(Correction& corr, hipStream_t stream);
 // vnrAmdCorrectionSetResidentForm: a correction that holds nothing on the device only notes the form, any other is converted at once
 void correction_set_resident_form(Correction& corr, int form, hipStream_t stream);
+// vnrAmdCorrectionSerializePackedToDevice: the "VNRCORP1" bytes into device memory, header and entries from the host, table and planes
+// device to device (made resident in the current form's way first).  d_bytes null: only *size.  Returns after completion.
+void correction_serialize_packed_to_device(Correction& corr, void* d_bytes, size_t capacity, size_t* size, hipStream_t consumer);
+
+// guided_sampler.hip: the hierarchical inclusive scan of n uint64 in place (block scans, the block sums scanned the same way level by
+// level, offsets added on the way down); scratch is grown to the upper levels' size.  Enqueued on s, not synchronised.
+void device_inclusive_scan(uint64_t* d_data, uint64_t n, DeviceBuffer<uint64_t>& scratch, hipStream_t s);
 
 // vnrAmdCorrectionRate (include/vnr_amd.h, "corrections to a byte budget"), field for field: what build_correction at eps followed by
 // both serialisations would report
@@ -321,6 +332,11 @@ public:
   // correction applied, in whichever form is resident (type and range are the correction's; out.type is ignored); only the box's
   // voxels are evaluated.  verify_params: refuse unless the parameters hash to what the correction was built on.
   std::shared_ptr<Correction> build_correction(const DeviceSource& ref, float range_lo, float range_hi, double eps);
+  // build_correction_packed: the same correction, observable for observable, built straight into the PACKED resident form: one pass in
+  // the packed form's order over all cells (a wave a group: nbits per group, the per-cell pairs, both error reports), n_cells pairs
+  // through the host, then the planes of the groups that store any from a second evaluation of those groups alone.  No fixed-width
+  // code is ever formed and no code crosses to the host.
+  std::shared_ptr<Correction> build_correction_packed(const DeviceSource& ref, float range_lo, float range_hi, double eps);
   void decode_to_device_corrected(Correction& corr, const DeviceTarget& out, const int box_lo[3], const int box_size[3], bool verify_params);
   // correction_rates: for each of n_eps (1 .. 64) tolerances exactly the counts and the sizes in both serialised forms that
   // build_correction(ref, range, eps[k]) would give, from ONE chunked evaluation of the network; nothing is built, `ref` is only read,

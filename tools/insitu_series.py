@@ -28,6 +28,11 @@ ingest time are printed.
                          vnrAmdCreateCorrectionFromPackedBytes).  Per step: the packed bytes, the fixed-width bytes over them, the
                          compressed bytes and the ratio with the packed form, the time of the device pack and of the first corrected
                          decode of a correction read from the packed bytes (upload, unpack on the device, apply)
+  --direct               with --error-bound: the correction built straight into the bit planes on the device
+                         (vnrAmdNeuralVolumeBuildCorrectionPacked) beside vnrAmdNeuralVolumeBuildCorrection followed by
+                         vnrAmdCorrectionSerializePacked, alternating in one process, max(--repeat, 10) samples each after a warm-up.
+                         Per step: min, median and max of both and of the direct build plus the one download of its bytes, the bytes each path
+                         leaves on the device, and whether both gave the same bytes and report (checked here)
   --resident FORM        with --error-bound: fixed | packed, the resident form of each step's correction, set before the corrected
                          decode (vnrAmdCorrectionSetResidentForm); packed keeps the bit planes and an index on the device and no
                          fixed-width payload.  Per step: the form and the bytes the correction holds on the device     [fixed]
@@ -75,6 +80,12 @@ upload of the packed payload, the unpack kernel and the apply; each repeat reads
 clock).  The kernels are correction_pack_measure_kernel, correction_pack_planes_kernel and correction_unpack_kernel.  With
 --resident packed the form is set on the fresh correction first: the upload of the packed payload and of the index, and the apply
 that reads the planes (correction_apply_planes_kernel); no unpack.
+
+The --direct times are host clocks around whole calls: "build_pack" is BuildCorrection plus SerializePacked on its result (two
+evaluations of the whole grid, the fixed-width codes to the host, the device pack, the packed bytes to the host), "direct" is
+BuildCorrectionPacked alone (one evaluation of the whole grid, one of the groups that store planes; table and planes stay on the
+device), "direct_and_bytes" adds the SerializePacked that downloads them.  The kernels are correction_direct_measure_kernel,
+correction_direct_index_kernel, correction_direct_list_kernel and correction_direct_planes_kernel.
 
 The --roi times are host clocks around whole calls as well, each warmed up once: "roi_apply" evaluates the network for the box's
 voxels alone and applies the correction in the resident form, "roi_plain_decode" is DecodeToDevice of the same box.
@@ -219,6 +230,43 @@ def error_bound(neural, ptr, dtype, strides, dims, ghost, value_range, eps, repe
     return row
 
 
+def direct_build(neural, ptr, dtype, strides, value_range, eps, repeat):
+    """-> the --direct columns of one step: vnrAmdNeuralVolumeBuildCorrectionPacked beside vnrAmdNeuralVolumeBuildCorrection followed by
+    vnrAmdCorrectionSerializePacked, alternating in this process, max(repeat, 10) samples each after one warm-up each; min and max"""
+    def two_calls():
+        t0 = time.perf_counter()
+        c = api.vnrNeuralVolumeBuildCorrection(neural, ptr, dtype, eps, strides, value_range)
+        blob = c.to_packed_bytes()
+        return c, blob, (time.perf_counter() - t0) * 1e3, None
+
+    def direct():
+        t0 = time.perf_counter()
+        c = api.vnrNeuralVolumeBuildCorrectionPacked(neural, ptr, dtype, eps, strides, value_range)
+        t1 = time.perf_counter()
+        residency = c.residency()                     # (as the call leaves it: before the bytes are asked for)
+        t2 = time.perf_counter()
+        blob = c.to_packed_bytes()                    # the one download of table plus planes
+        return c, blob, (t1 - t0) * 1e3, (t1 - t0 + time.perf_counter() - t2) * 1e3, residency
+
+    times = {"build_pack": [], "direct": [], "direct_and_bytes": []}
+    equal, row = True, {}
+    for k in range(1 + max(repeat, 10)):
+        c2, blob2, ms2, _ = two_calls()
+        c1, blob1, ms1, ms1b, residency = direct()
+        if k:      # (k == 0 warms both up)
+            times["build_pack"].append(ms2); times["direct"].append(ms1); times["direct_and_bytes"].append(ms1b)
+        equal = equal and blob1 == blob2
+        if k == 0:     # once a step: the fixed-width bytes and the report as well
+            equal = equal and c1.to_bytes() == c2.to_bytes() and repr(c1.info()) == repr(c2.info())
+            row.update(direct_device_bytes=residency["device_bytes"], build_pack_device_bytes=c2.residency()["device_bytes"],
+                       direct_packed_bytes=len(blob1))
+        c1.release(); c2.release()
+    for name, t in times.items():
+        row[name + "_min_ms"], row[name + "_median_ms"], row[name + "_max_ms"] = round(min(t), 4), round(statistics.median(t), 4), round(max(t), 4)
+    row.update(direct_samples=len(times["direct"]), direct_equals_build_pack=equal)
+    return row
+
+
 def byte_budget(neural, ptr, dtype, strides, dims, value_range, max_bytes, form, rounds, repeat):
     """-> the --byte-budget columns of one step.  `ptr` is the step's own device array (the reference of the correction)."""
     eps_hi = api.vnrNeuralVolumeErrorAgainstDevice(neural, ptr, dtype, strides, None, value_range)["max_abs"]
@@ -308,6 +356,7 @@ def main(argv=None):
     p.add_argument("--round-trip", action="store_true")
     p.add_argument("--error-bound", type=float, default=None, metavar="EPS")
     p.add_argument("--packed", action="store_true")
+    p.add_argument("--direct", action="store_true")
     p.add_argument("--resident", default="fixed", choices=["fixed", "packed"])
     p.add_argument("--roi", default=None, metavar="x0,y0,z0,sx,sy,sz")
     p.add_argument("--byte-budget", type=int, default=None, metavar="BYTES")
@@ -324,8 +373,8 @@ def main(argv=None):
         p.error("--round-trip needs a trained network: --steps-per-frame > 0")
     if a.error_bound is not None and (not a.steps_per_frame or not a.error_bound >= 0.0 or a.error_bound == float("inf")):
         p.error("--error-bound needs a trained network (--steps-per-frame > 0) and a finite EPS >= 0")
-    if a.packed and a.error_bound is None:
-        p.error("--packed needs --error-bound EPS")
+    if (a.packed or a.direct) and a.error_bound is None:
+        p.error("--packed and --direct need --error-bound EPS")
     if a.byte_budget is not None and (not a.steps_per_frame or a.byte_budget < 0 or not 0 <= a.budget_rounds <= 8):
         p.error("--byte-budget needs a trained network (--steps-per-frame > 0), BYTES >= 0 and --budget-rounds 0 .. 8")
     roi = None
@@ -391,6 +440,8 @@ def main(argv=None):
                 row.update(round_trip(neural, ptr, dtype, strides, dims, a.ghost, used, a.repeat, coords))
             if a.error_bound is not None:
                 row.update(error_bound(neural, ptr, dtype, strides, dims, a.ghost, used, a.error_bound, a.repeat, a.packed, a.resident, roi, step))
+                if a.direct:
+                    row.update(direct_build(neural, ptr, dtype, strides, used, a.error_bound, a.repeat))
             if a.byte_budget is not None:
                 row.update(byte_budget(neural, ptr, dtype, strides, dims, used, a.byte_budget, a.budget_form, a.budget_rounds, a.repeat))
         d.free()

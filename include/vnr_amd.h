@@ -499,6 +499,52 @@ vnrAmdCorrection vnrAmdNeuralVolumeBuildCorrectionWithinBytes(vnrAmdVolume neura
 vnrAmdCorrection vnrAmdNeuralVolumeBuildCorrectionPacked(vnrAmdVolume neural, const void* d_ref, int value_type, const int64_t strides[3],
                                                          float range_lo, float range_hi, double eps, void* stream);
 int  vnrAmdCorrectionSerializePackedToDevice(vnrAmdCorrection, void* d_bytes, size_t capacity, size_t* size, void* stream);
+/* AMD extension: coded corrections.  A third serialised form of the same correction, "VNRCORC1": the same codes and header fields,
+ * either of the other two forms recoverable from it byte for byte.  It removes what the packed form still spends at low rates: a
+ * sign bit for every code, zeros included, and 64 bits for a plane however few of them are set.  It is a serialised form only: on
+ * the device a correction is resident as fixed-width codes or as bit planes, and no apply reads coded streams.
+ *
+ * Little-endian.  The header above with magic "VNRCORC1", version 1 and payload_bytes the size of the coded payload; the same
+ * n_flagged entries {u32 cell, u32 width}; then the payload:
+ *   1. the cell table: one u32 per flagged cell in entry order, the 64-bit words of that cell's stream; zero bytes up to a multiple of 8;
+ *   2. the cell streams, in entry order.
+ * A stream is a run of u64 words; stream bit i is bit i % 64 of word i / 64; a field of n bits is appended least significant bit
+ * first; every cell's stream starts on a word and is filled up with zero bits to a whole word.  A cell's stream is the records of
+ * its groups in order; the groups are the packed form's (64 consecutive codes in the order lx + cx * (ly + cy * lz), the last group
+ * filled with codes of 0: ceil(voxels / 64) groups a cell).
+ * Group record, kinds 0 and 1, with q_l the sign-extended code of lane l, m_l = |q_l| (0 .. 2^31) and s_l = (q_l < 0):
+ *   1. mbits, 7 bits: the bit length of the largest m_l; if it is 0 the record ends here;
+ *   2. for b = mbits - 1 down to 0, with P the set of lanes whose m_l has bit b and c = |P|:
+ *        c <= 9: one bit 1, then c in 4 bits, then the lanes of P ascending, 6 bits each;
+ *        else:   one bit 0, then 64 bits, bit l set for l in P
+ *      (a list costs 5 + 6 c bits against 65, so 9 is the largest count that pays);
+ *   3. for every lane with m_l != 0, ascending: one bit s_l.
+ * Group record, kind 2 (verbatim patterns): m_l is the stored bit pattern, mbits is 0 .. 64, and there is no step 3.
+ * The writer is canonical: what the reader accepts, the writer gives back byte for byte.
+ *
+ * CreateCorrectionFromCodedBytes is host only and validates everything before it allocates anything by the bytes' say; each rule is
+ * refused by name under "malformed coded correction bytes: ": all header and entry rules of CreateCorrectionFromBytes; cell table
+ * padding not zero; a payload shorter than the cell table; a payload size that differs from the sum the cell table gives; a record
+ * that runs past its cell's words; a table entry that differs from the length its records have; stream padding not zero; mbits
+ * above 8 * width; a code that does not fit the width (kinds 0 and 1: m = 2^(8 width - 1) only with the sign set, nothing larger);
+ * an empty top plane; a list count above 9; a plane stored dense with 9 or fewer bits set; list lanes not strictly ascending; a bit
+ * beyond the cell's voxels.  At its first use on the device the coded payload is uploaded as it is and decoded there by one kernel,
+ * a cell a wave, into the packed resident form (the FIXED resident form, the default, then unpacks as for packed bytes), and the
+ * coded copy on the device is released; a correction that is only serialised again, or queried, is transcoded on the host and asks
+ * for no device.  GetResidency reports what it reports for the same correction read from packed bytes.
+ *
+ * SerializeCoded returns the bytes (vnrAmdFreeHost), cached like SerializePacked's: encoded on the device from whichever form is
+ * resident, codes or planes, in two passes (the records' lengths in closed form from one ballot and popcount a plane; a device
+ * scan; the cells' streams assembled in LDS and stored as whole words), no code or plane crossing to the host; a correction that
+ * holds nothing on the device (read from bytes of any form and never applied, or without a flagged cell) is transcoded on the host.
+ * SerializeCodedToDevice writes the same bytes into device memory, encoded straight into the destination; its arguments, its
+ * size-only call (d_bytes == NULL) and its refusals are SerializePackedToDevice's.
+ * Not built: the rate call and BuildCorrectionWithinBytes do not know the coded form (vnrAmdCorrectionRate's layout is ABI); there is
+ * no apply straight from coded streams; there is no prediction across voxels.
+ * Errors: a null handle, result or bytes; capacity < *size (both are named, nothing is written); malformed bytes, each rule by name. */
+int  vnrAmdCorrectionSerializeCoded(vnrAmdCorrection, void** bytes, size_t* size);
+vnrAmdCorrection vnrAmdCreateCorrectionFromCodedBytes(const void* bytes, size_t size);
+int  vnrAmdCorrectionSerializeCodedToDevice(vnrAmdCorrection, void* d_bytes, size_t capacity, size_t* size, void* stream);
 /* hash-grid encode only (tcnn_impl_decoder.cu:177-230, column = level*F + f): fp16 [n][padded_width] */
 int    vnrAmdNeuralVolumeEncode(vnrAmdVolume, size_t n, const float* d_coords, uint16_t* d_features, void* stream);
 /* AMD extension: state of the brick image, the de-hashed inference copy of the hashed levels (csrc/network.h).  It is built

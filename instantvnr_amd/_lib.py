@@ -289,6 +289,9 @@ def lib():
     sig("vnrAmdNeuralVolumeBuildCorrectionWithinBytes", P, P, P, I, I64P, F, F, U64, I, D, I, P, C.POINTER(CorrectionBudget))
     sig("vnrAmdNeuralVolumeBuildCorrectionPacked", P, P, P, I, I64P, F, F, D, P)
     sig("vnrAmdCorrectionSerializePackedToDevice", I, P, P, SZ, C.POINTER(SZ), P)
+    sig("vnrAmdCorrectionSerializeCoded", I, P, C.POINTER(P), C.POINTER(SZ))
+    sig("vnrAmdCreateCorrectionFromCodedBytes", P, P, SZ)
+    sig("vnrAmdCorrectionSerializeCodedToDevice", I, P, P, SZ, C.POINTER(SZ), P)
     _lib = L
     return L
 

@@ -511,7 +511,8 @@ def vnrNeuralVolumeErrorAgainstDevice(v, d_ptr, dtype, strides=None, box=None, v
 
 class Correction(_Handle):
     """an error-bound correction (include/vnr_amd.h, "error-bounded round trip"): built by vnrNeuralVolumeBuildCorrection or loaded
-    with Correction.from_bytes / from_packed_bytes; to_bytes() or the smaller to_packed_bytes() beside params.json is the compressed field"""
+    with Correction.from_bytes / from_packed_bytes / from_coded_bytes; to_bytes(), the smaller to_packed_bytes() or the still smaller
+    to_coded_bytes() beside params.json is the compressed field"""
     _release = "vnrAmdReleaseCorrection"
 
     def info(self):
@@ -567,6 +568,38 @@ class Correction(_Handle):
         if not ptr:
             raise VnrAmdError("null device data")
         check(lib().vnrAmdCorrectionSerializePackedToDevice(self.h, C.c_void_p(ptr), int(capacity), C.byref(n), C.c_void_p(stream) if stream else None))
+        return n.value
+
+    def to_coded_bytes(self):
+        """the coded form (include/vnr_amd.h, "coded corrections"): encoded on the device from whichever form is resident, once, or
+        on the host if the correction holds nothing on the device; the bytes it was read from if it came from_coded_bytes"""
+        out = C.c_void_p()
+        n = C.c_size_t()
+        check(lib().vnrAmdCorrectionSerializeCoded(self.h, C.byref(out), C.byref(n)))
+        b = C.string_at(out, n.value)
+        lib().vnrAmdFreeHost(out)
+        return b
+
+    @classmethod
+    def from_coded_bytes(cls, b):
+        """host only: the bytes are validated here, uploaded as they are and decoded on the device by the first apply"""
+        b = bytes(b)
+        return cls(lib().vnrAmdCreateCorrectionFromCodedBytes(b, len(b)))
+
+    def to_coded_device(self, d_ptr=None, stream=None):
+        """to_coded_bytes() written into device memory, encoded there straight into the destination.  d_ptr None -> the size in
+        bytes; a DeviceArray (its whole size is the capacity) or (address, capacity) -> the bytes written"""
+        n = C.c_size_t()
+        if d_ptr is None:
+            check(lib().vnrAmdCorrectionSerializeCodedToDevice(self.h, None, 0, C.byref(n), None))
+            return n.value
+        if isinstance(d_ptr, DeviceArray):
+            ptr, capacity = d_ptr.ptr, d_ptr.nbytes
+        else:
+            ptr, capacity = d_ptr
+        if not ptr:
+            raise VnrAmdError("null device data")
+        check(lib().vnrAmdCorrectionSerializeCodedToDevice(self.h, C.c_void_p(ptr), int(capacity), C.byref(n), C.c_void_p(stream) if stream else None))
         return n.value
 
     RESIDENT_FORMS = {"fixed": 0, "packed": 1}

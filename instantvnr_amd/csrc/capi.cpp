@@ -615,6 +615,7 @@ int vnrAmdCorrectionSerializePackedToDevice(vnrAmdCorrection c, void* d_bytes, s
   return guarded([&]() {
     Correction* k = as_correction(c);
     if (!size) throw std::runtime_error("null result");
+    if (!k->planes_uploaded) k->transcode_coded_on_host();   // (read from coded bytes and never used on the device: no device is asked for)
     if (!Runtime::get().ready() && (d_bytes || (!k->data.cells.empty() && !k->has_packed))) Runtime::get().init(-1);
     correction_serialize_packed_to_device(*k, d_bytes, capacity, size, (hipStream_t)stream);
   });
@@ -708,6 +709,7 @@ int vnrAmdCorrectionSerializePacked(vnrAmdCorrection c, void** bytes, size_t* si
   return guarded([&]() {
     Correction* k = as_correction(c);
     if (!bytes || !size) throw std::runtime_error("null result");
+    if (!k->planes_uploaded) k->transcode_coded_on_host();   // (read from coded bytes and never used on the device: no device is asked for)
     if (!k->has_packed) {   // the device pack, once
       if (!k->data.cells.empty() && !Runtime::get().ready()) Runtime::get().init(-1);
       correction_packed_payload(*k, Runtime::get().stream);
@@ -728,6 +730,41 @@ vnrAmdCorrection vnrAmdCreateCorrectionFromPackedBytes(const void* bytes, size_t
     k->has_packed = k->from_packed = true;
     k->max_abs_before = std::numeric_limits<double>::quiet_NaN();   // as CreateCorrectionFromBytes
     return new vnrAmdCorrection_t{std::move(k)};
+  });
+}
+int vnrAmdCorrectionSerializeCoded(vnrAmdCorrection c, void** bytes, size_t* size)
+{
+  return guarded([&]() {
+    Correction* k = as_correction(c);
+    if (!bytes || !size) throw std::runtime_error("null result");
+    // (a correction that holds codes or planes on the device has initialised the runtime; any other is transcoded on the host)
+    const std::vector<uint8_t> b = correction_coded_write(k->data.h, k->data.cells, correction_coded_payload(*k, Runtime::get().stream));
+    *bytes = dup_bytes(b.data(), b.size());
+    *size = b.size();
+  });
+}
+vnrAmdCorrection vnrAmdCreateCorrectionFromCodedBytes(const void* bytes, size_t size)
+{
+  return guarded_new<vnrAmdCorrection_t>([&]() {
+    auto k = std::make_shared<Correction>();
+    CorrectionCoded p = correction_coded_parse(bytes, size);
+    k->data.h = p.h;
+    k->data.cells = std::move(p.cells);
+    k->coded_payload = std::move(p.payload);
+    k->group_table = std::move(p.group_nbits);
+    k->has_coded = k->from_coded = true;
+    if (k->data.cells.empty()) k->has_packed = k->from_packed = true;   // no group, no plane: the packed payload is empty, too
+    k->max_abs_before = std::numeric_limits<double>::quiet_NaN();   // as CreateCorrectionFromBytes
+    return new vnrAmdCorrection_t{std::move(k)};
+  });
+}
+int vnrAmdCorrectionSerializeCodedToDevice(vnrAmdCorrection c, void* d_bytes, size_t capacity, size_t* size, void* stream)
+{
+  return guarded([&]() {
+    Correction* k = as_correction(c);
+    if (!size) throw std::runtime_error("null result");
+    if (!Runtime::get().ready() && d_bytes) Runtime::get().init(-1);   // (the size alone of a correction that lives on the host asks for no device)
+    correction_serialize_coded_to_device(*k, d_bytes, capacity, size, (hipStream_t)stream);
   });
 }
 int vnrAmdNeuralVolumeDecodeToDeviceCorrected(vnrAmdVolume v, vnrAmdCorrection c, void* d_out, const int64_t strides[3], void* stream, int verify_params)

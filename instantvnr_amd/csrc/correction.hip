@@ -875,6 +875,8 @@ void correction_make_resident(Correction& corr, hipStream_t stream)
 {
   const CorrectionData& d = corr.data;
   if (d.cells.empty()) return;
+  // read from coded bytes and first used here: the streams are decoded on the device (correction_code.hip), the planes are then resident
+  if (corr.coded_pending() && !corr.planes_uploaded && !corr.uploaded && !corr.payload_uploaded) correction_decode_coded_on_device(corr, stream);
   const uint64_t n_cells = correction_n_cells(d.h.dims);
   if (corr.resident_form == 0) {
     if (!corr.uploaded) {

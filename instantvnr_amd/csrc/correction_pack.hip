@@ -162,7 +162,9 @@ uint32_t cell_blocks(size_t n_cells) { return (uint32_t)std::min<size_t>(n_cells
 void unpack_on_device(Correction& corr, hipStream_t stream)
 {
   const CorrectionData& d = corr.data;
-  if (!corr.has_packed) correction_packed_payload(corr, stream);   // (a direct build: the group table has not been on the host yet)
+  // (a direct build: the group table has not been on the host yet; one decoded from coded bytes on the device has the parse's)
+  if (!corr.has_packed && !(corr.coded_pending() && corr.planes_uploaded)) correction_packed_payload(corr, stream);
+  const uint8_t* table = corr.has_packed ? corr.packed_payload.data() : corr.group_table.data();
   const std::vector<PackCell> cells = make_pack_cells(d);
   const uint64_t table_bytes = correction_group_table_bytes(correction_n_groups(d.h, d.cells));
   // the cells' first plane words, from the table (validated when the bytes were read)
@@ -171,9 +173,9 @@ void unpack_on_device(Correction& corr, hipStream_t stream)
   for (size_t i = 0; i < cells.size(); ++i) {
     word0[i] = words;
     const uint64_t groups = correction_cell_groups(cells[i].voxels);
-    for (uint64_t k = 0; k < groups; ++k) words += corr.packed_payload[cells[i].group0 + k];
+    for (uint64_t k = 0; k < groups; ++k) words += table[cells[i].group0 + k];
   }
-  if (corr.packed_payload.size() != table_bytes + 8 * words) throw std::runtime_error("the packed payload does not have the size its group table gives");
+  if ((corr.has_packed ? corr.packed_payload.size() : corr.d_packed.bytes()) != table_bytes + 8 * words) throw std::runtime_error("the packed payload does not have the size its group table gives");
   DeviceBuffer<PackCell> d_cells(MemTag::Network);
   DeviceBuffer<uint64_t> d_word0(MemTag::Network);
   DeviceBuffer<uint8_t> d_packed(MemTag::Network);
@@ -210,6 +212,16 @@ const std::vector<uint8_t>& correction_packed_payload(Correction& corr, hipStrea
   const CorrectionData& d = corr.data;
   if (d.cells.empty()) {   // no group, no plane
     corr.has_packed = true;
+    return corr.packed_payload;
+  }
+  if (corr.coded_pending()) {   // read from coded bytes: the planes as the device decoded them, downloaded once, or transcoded on the host
+    if (corr.planes_uploaded) {
+      corr.packed_payload.resize(corr.d_packed.count);
+      corr.d_packed.download(corr.packed_payload.data(), corr.d_packed.count, stream);   // (synchronises)
+      corr.has_packed = corr.from_packed = true;
+    } else {
+      corr.transcode_coded_on_host();
+    }
     return corr.packed_payload;
   }
   if (corr.direct) {   // built straight into the planes: table and planes as they lie on the device, downloaded once

@@ -11,6 +11,7 @@
 #include "common.h"
 #include "correction_format.h"
 #include "correction_packed_format.h"
+#include "correction_coded_format.h"
 #include "json.h"
 #include "network.h"
 #include "ooc_sampler.h"
@@ -141,9 +142,24 @@ struct Correction {
   // fixed-width payload anywhere and packed_payload is empty until correction_packed_payload downloads d_packed (has_packed); from
   // then on the correction behaves like one read from packed bytes.
   bool direct = false;
+  // The coded form (correction_coded_format.h, correction_code.hip).  coded_payload: the cell table and the streams, either what the
+  // correction was read from (from_coded) or the cached result of vnrAmdCorrectionSerializeCoded.  A correction read from coded bytes
+  // holds nothing else until its first use: on the host alone it is transcoded into packed_payload there (from then on it behaves like
+  // one read from packed bytes); at a first use on the device the streams are decoded into d_packed there, and the host takes the
+  // packed payload from there when it first needs it.  group_table is the parse's by-product, the packed form's nbits of every group.
+  std::vector<uint8_t> coded_payload, group_table;
+  bool has_coded = false, from_coded = false;
+  bool coded_pending() const { return from_coded && !has_packed; }   // the host holds no packed payload yet
+  void transcode_coded_on_host()
+  {
+    if (!coded_pending()) return;
+    packed_payload = correction_coded_to_packed(data.h, data.cells, coded_payload, group_table);
+    has_packed = from_packed = true;
+  }
   const uint64_t* d_planes() const { return reinterpret_cast<const uint64_t*>(d_packed.ptr + correction_group_table_bytes(d_plane_groups.count)); }
   const std::vector<uint8_t>& host_payload()   // data.payload, unpacked on the host at its first use (direct: has_packed comes first)
   {
+    transcode_coded_on_host();
     if ((from_packed || (direct && has_packed)) && data.payload.empty() && !data.cells.empty()) data.payload = correction_unpack(data.h, data.cells, packed_payload);
     return data.payload;
   }
@@ -162,6 +178,16 @@ void correction_set_resident_form(Correction& corr, int form, hipStream_t stream
 // vnrAmdCorrectionSerializePackedToDevice: the "VNRCORP1" bytes into device memory, header and entries from the host, table and planes
 // device to device (made resident in the current form's way first).  d_bytes null: only *size.  Returns after completion.
 void correction_serialize_packed_to_device(Correction& corr, void* d_bytes, size_t capacity, size_t* size, hipStream_t consumer);
+// correction_code.hip.  The coded payload (cell table and streams): encoded on the device from whichever form is resident, no code or
+// plane crossing to the host, or, for a correction that holds nothing on the device, transcoded on the host without asking for one;
+// cached in coded_payload.  Has synchronised on return.
+const std::vector<uint8_t>& correction_coded_payload(Correction& corr, hipStream_t stream);
+// vnrAmdCorrectionSerializeCodedToDevice: the "VNRCORC1" bytes into device memory, encoded there straight into the destination (from
+// the host copy where the correction holds nothing on the device).  d_bytes null: only *size.  Returns after completion.
+void correction_serialize_coded_to_device(Correction& corr, void* d_bytes, size_t capacity, size_t* size, hipStream_t consumer);
+// the first use on the device of a correction read from coded bytes: the streams uploaded as they are and decoded by one kernel into
+// the packed resident form (d_packed and its index, as correction_make_resident leaves them); the coded copy on the device is released
+void correction_decode_coded_on_device(Correction& corr, hipStream_t stream);
 
 // guided_sampler.hip: the hierarchical inclusive scan of n uint64 in place (block scans, the block sums scanned the same way level by
 // level, offsets added on the way down); scratch is grown to the upper levels' size.  Enqueued on s, not synchronised.

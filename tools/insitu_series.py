@@ -33,6 +33,13 @@ ingest time are printed.
                          vnrAmdCorrectionSerializePacked, alternating in one process, max(--repeat, 10) samples each after a warm-up.
                          Per step: min, median and max of both and of the direct build plus the one download of its bytes, the bytes each path
                          leaves on the device, and whether both gave the same bytes and report (checked here)
+  --coded                with --error-bound: the coded form ("VNRCORC1": sparse bit planes as lists of lanes, signs for the non-zero
+                         codes alone) of the correction built straight into the bit planes.  Per step: the packed bytes, the coded
+                         bytes, bits a voxel of a flagged cell in both forms and the compressed ratio with each; min, median and max of
+                         vnrAmdCorrectionSerializeCodedToDevice and vnrAmdCorrectionSerializePackedToDevice of that correction
+                         (alternating, max(--repeat, 10) samples each after one warm-up each); the first corrected decode of a
+                         correction read from the coded bytes beside one read from the packed bytes; and whether the correction
+                         read back from the coded bytes serialises to the original's packed bytes
   --resident FORM        with --error-bound: fixed | packed, the resident form of each step's correction, set before the corrected
                          decode (vnrAmdCorrectionSetResidentForm); packed keeps the bit planes and an index on the device and no
                          fixed-width payload.  Per step: the form and the bytes the correction holds on the device     [fixed]
@@ -80,6 +87,13 @@ upload of the packed payload, the unpack kernel and the apply; each repeat reads
 clock).  The kernels are correction_pack_measure_kernel, correction_pack_planes_kernel and correction_unpack_kernel.  With
 --resident packed the form is set on the fresh correction first: the upload of the packed payload and of the index, and the apply
 that reads the planes (correction_apply_planes_kernel); no unpack.
+
+The --coded times are host clocks around whole calls: "serialize_coded_to_device" is pass 1 (correction_code_measure_kernel), the
+device scan of the cells' words, one count to the host and pass 2 (correction_code_write_kernel) straight into the destination, from
+the resident planes; "serialize_packed_to_device" copies the resident table and planes device to device.  "coded_first_apply" is the
+first vnrAmdNeuralVolumeDecodeToDeviceCorrected of a correction just read from the coded bytes (the upload of the coded payload and of
+the index, correction_code_decode_kernel, in the FIXED resident form the unpack kernel, and the apply), "packed_first_apply_again" the
+same of one just read from the packed bytes, alternating; the host's validation is outside both.
 
 The --direct times are host clocks around whole calls: "build_pack" is BuildCorrection plus SerializePacked on its result (two
 evaluations of the whole grid, the fixed-width codes to the host, the device pack, the packed bytes to the host), "direct" is
@@ -267,6 +281,68 @@ def direct_build(neural, ptr, dtype, strides, value_range, eps, repeat):
     return row
 
 
+def coded_form(neural, ptr, dtype, strides, dims, ghost, value_range, eps, repeat, resident):
+    """-> the --coded columns of one step: the coded form beside the packed form of the correction that
+    vnrAmdNeuralVolumeBuildCorrectionPacked leaves resident as bit planes"""
+    corr = api.vnrNeuralVolumeBuildCorrectionPacked(neural, ptr, dtype, eps, strides, value_range)
+    raw = dims[0] * dims[1] * dims[2] * dtype.itemsize
+    n_params = len(api.vnrNeuralVolumeSerializeParams(neural))
+    sizes = {"packed": corr.to_packed_device(), "coded": corr.to_coded_device()}
+    bufs = {k: api.DeviceArray((max(v, 1),), np.uint8) for k, v in sizes.items()}
+    write = {"packed": corr.to_packed_device, "coded": corr.to_coded_device}
+    times = {"packed": [], "coded": []}
+    for k in range(1 + max(repeat, 10)):      # (k == 0 warms both up)
+        for form in ("coded", "packed"):
+            t0 = time.perf_counter()
+            written = write[form](bufs[form])
+            if k:
+                times[form].append((time.perf_counter() - t0) * 1e3)
+            assert written == sizes[form]
+    coded = bufs["coded"].numpy()[:sizes["coded"]].tobytes()
+    packed = bufs["packed"].numpy()[:sizes["packed"]].tobytes()
+    for b in bufs.values():
+        b.free()
+    n_flagged = int(np.frombuffer(coded, "<u4", 1, 28)[0])
+    cells = np.frombuffer(coded, "<u4", 2 * n_flagged, 104)[0::2].astype(np.int64)
+    m = [-(-d // 16) for d in dims]
+    extent = lambda d, i: np.minimum(16, d - 16 * i)
+    voxels = int((extent(dims[0], cells % m[0]) * extent(dims[1], cells // m[0] % m[1]) * extent(dims[2], cells // (m[0] * m[1]))).sum())
+    head = 104 + 8 * n_flagged
+    row = {"coded_flagged_cells": n_flagged, "coded_flagged_voxels": voxels, "packed_form_bytes": len(packed), "coded_form_bytes": len(coded),
+           "packed_bits_per_flagged_voxel": round(8 * (len(packed) - head) / max(voxels, 1), 4),
+           "coded_bits_per_flagged_voxel": round(8 * (len(coded) - head) / max(voxels, 1), 4),
+           "packed_form_ratio": round(raw / (n_params + len(packed)), 3), "coded_form_ratio": round(raw / (n_params + len(coded)), 3)}
+    for form, t in times.items():
+        row.update({f"serialize_{form}_to_device_min_ms": round(min(t), 4), f"serialize_{form}_to_device_median_ms": round(statistics.median(t), 4),
+                    f"serialize_{form}_to_device_max_ms": round(max(t), 4)})
+    row["serialize_samples"] = len(times["coded"])
+    same = packed == corr.to_packed_bytes() and coded == corr.to_coded_bytes()
+    # the first corrected decode of a correction read from either form
+    padded = tuple(d + 2 * ghost for d in dims)
+    out = api.DeviceArray((padded[2], padded[1], padded[0]), dtype)
+    first = (ghost + ghost * padded[0] + ghost * padded[0] * padded[1]) * dtype.itemsize
+    applies = {"coded": [], "packed": []}
+    stored = {}
+    for k in range(1 + repeat):
+        for form, read, blob in (("coded", api.Correction.from_coded_bytes, coded), ("packed", api.Correction.from_packed_bytes, packed)):
+            fresh = read(blob)
+            fresh.set_resident_form(resident)
+            ms = timed(lambda: api.vnrNeuralVolumeDecodeToDeviceCorrected(neural, fresh, out.ptr + first, strides), 1)[1]
+            if k:
+                applies[form].append(ms)
+            else:
+                stored[form] = out.numpy().tobytes()
+                if form == "coded":
+                    same = same and fresh.to_packed_bytes() == packed
+            fresh.release()
+    out.free()
+    corr.release()
+    row.update(coded_first_apply_ms=round(min(applies["coded"]), 4), coded_first_apply_median_ms=round(statistics.median(applies["coded"]), 4),
+               packed_first_apply_again_ms=round(min(applies["packed"]), 4), packed_first_apply_again_median_ms=round(statistics.median(applies["packed"]), 4),
+               coded_reads_back_to_packed=bool(same), coded_decodes_like_packed=stored["coded"] == stored["packed"])
+    return row
+
+
 def byte_budget(neural, ptr, dtype, strides, dims, value_range, max_bytes, form, rounds, repeat):
     """-> the --byte-budget columns of one step.  `ptr` is the step's own device array (the reference of the correction)."""
     eps_hi = api.vnrNeuralVolumeErrorAgainstDevice(neural, ptr, dtype, strides, None, value_range)["max_abs"]
@@ -357,6 +433,7 @@ def main(argv=None):
     p.add_argument("--error-bound", type=float, default=None, metavar="EPS")
     p.add_argument("--packed", action="store_true")
     p.add_argument("--direct", action="store_true")
+    p.add_argument("--coded", action="store_true")
     p.add_argument("--resident", default="fixed", choices=["fixed", "packed"])
     p.add_argument("--roi", default=None, metavar="x0,y0,z0,sx,sy,sz")
     p.add_argument("--byte-budget", type=int, default=None, metavar="BYTES")
@@ -373,8 +450,8 @@ def main(argv=None):
         p.error("--round-trip needs a trained network: --steps-per-frame > 0")
     if a.error_bound is not None and (not a.steps_per_frame or not a.error_bound >= 0.0 or a.error_bound == float("inf")):
         p.error("--error-bound needs a trained network (--steps-per-frame > 0) and a finite EPS >= 0")
-    if (a.packed or a.direct) and a.error_bound is None:
-        p.error("--packed and --direct need --error-bound EPS")
+    if (a.packed or a.direct or a.coded) and a.error_bound is None:
+        p.error("--packed, --direct and --coded need --error-bound EPS")
     if a.byte_budget is not None and (not a.steps_per_frame or a.byte_budget < 0 or not 0 <= a.budget_rounds <= 8):
         p.error("--byte-budget needs a trained network (--steps-per-frame > 0), BYTES >= 0 and --budget-rounds 0 .. 8")
     roi = None
@@ -442,6 +519,8 @@ def main(argv=None):
                 row.update(error_bound(neural, ptr, dtype, strides, dims, a.ghost, used, a.error_bound, a.repeat, a.packed, a.resident, roi, step))
                 if a.direct:
                     row.update(direct_build(neural, ptr, dtype, strides, used, a.error_bound, a.repeat))
+                if a.coded:
+                    row.update(coded_form(neural, ptr, dtype, strides, dims, a.ghost, used, a.error_bound, a.repeat, a.resident))
             if a.byte_budget is not None:
                 row.update(byte_budget(neural, ptr, dtype, strides, dims, used, a.byte_budget, a.budget_form, a.budget_rounds, a.repeat))
         d.free()

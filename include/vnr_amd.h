@@ -426,8 +426,8 @@ int  vnrAmdNeuralVolumeDecodeBoxToDeviceCorrected(vnrAmdVolume neural, vnrAmdCor
  * groups of 64 codes, at least one; the result does not depend on it), in the packed form's order over all cells of the grid: one
  * wavefront takes one group, forms r once and then, per tolerance, the build's own quantiser, two wave maxima and a ballot, folded
  * per cell with integer atomics.  The call stores nothing in d_ref, changes no state of the volume and keeps nothing resident but
- * the chunk scratch every round-trip call shares; its own scratch is 8 bytes per macrocell and tolerance.  Only the n_eps results
- * cross to the host.
+ * the chunk scratch every round-trip call shares; its own scratch is 8 bytes per macrocell and tolerance (CorrectionRatesCoded below:
+ * 4 more, 12).  Only the n_eps results cross to the host.
  * Errors: BuildCorrection's; a null eps or out; n_eps outside 1 .. 64; an eps[k] that is negative, NaN or infinite (k and the value
  * are named).  These four are found before the volume is looked at.
  *
@@ -463,6 +463,49 @@ int vnrAmdNeuralVolumeCorrectionRates(vnrAmdVolume neural, const void* d_ref, in
 typedef struct vnrAmdCorrectionBudget { double eps; uint64_t bytes; double eps_tighter; uint64_t bytes_tighter; int rate_passes; } vnrAmdCorrectionBudget;
 vnrAmdCorrection vnrAmdNeuralVolumeBuildCorrectionWithinBytes(vnrAmdVolume neural, const void* d_ref, int value_type,
     const int64_t strides[3], float range_lo, float range_hi, uint64_t max_bytes, int form, double eps_hi, int rounds,
+    void* stream, vnrAmdCorrectionBudget* report);
+/* AMD extension: byte budgets in the coded form ("coded corrections" below, "VNRCORC1": the smallest form the library writes).
+ * vnrAmdCorrectionRate's layout is ABI and BuildCorrectionWithinBytes refuses every form but FIXED and PACKED; both stay exactly as
+ * they are, and the coded form has entry points of its own.
+ *
+ * CorrectionRatesCoded: the arguments, refusals and messages of CorrectionRates (the four that need no volume are found before the
+ * volume is looked at).  Entry k's `rate` is CorrectionRates' entry k bit for bit; beside it, EXACTLY what BuildCorrection(..., eps[k],
+ * ...) followed by SerializeCoded would give:
+ *   coded_stream_words      the sum over the flagged cells of the 64-bit words of the cell's stream
+ *   coded_payload_bytes     = pad8(4 n_flagged) + 8 coded_stream_words
+ *   coded_serialized_bytes  = 104 + 8 n_flagged + coded_payload_bytes
+ * All three are 0 where the entry is refused; an entry without a flagged cell has 0 words, 0 payload bytes and 104 serialised bytes.
+ * The network is still evaluated once per voxel per call whatever n_eps is, and only the results cross to the host.  The pass is
+ * CorrectionRates' with a compile-time variant of its kernel (CorrectionRates itself runs the kernel it always ran): after the
+ * quantiser, per group and tolerance, with m_l = |q_l| (kind 2: ref's bit pattern; lanes beyond a ragged cell's voxels 0) and mbits
+ * the bit length of the wave's largest m_l, one ballot and one popcount c for each plane b < mbits, 5 + 6 c bits for c <= 9 and 65
+ * otherwise, plus (kinds 0 and 1) one sign bit per lane with q_l != 0, folded per cell and tolerance with one integer atomic; every
+ * group of a flagged cell, the groups of zeros included, adds the 7 bits of its mbits; a cell's stream is that sum filled up to whole
+ * words.  Scratch: CorrectionRates' 8 bytes per macrocell and tolerance, and 4 more for this call.
+ *
+ * BuildCorrectionCodedWithinBytes: max_bytes bounds the size of SerializeCoded.  The search is BuildCorrectionWithinBytes' search,
+ * unchanged, fed with coded_serialized_bytes.  The tolerance it returns is then built by BuildCorrectionPacked, so the correction
+ * comes back in the PACKED resident form and no fixed-width payload is allocated at any point; the device encode then runs once,
+ * its size must equal the rate's figure (a difference is an internal error that names both) and its bytes stay cached for
+ * SerializeCoded and SerializeCodedToDevice.  report is BuildCorrectionWithinBytes', with bytes in the coded form.
+ * Coded sizes CAN grow with the tolerance, unlike FIXED and PACKED sizes: a lane whose magnitude falls from 4 to 3 sets two lower
+ * plane bits where it cleared one, which can push a plane from a list to the dense form.  The search's prefix / suffix wording
+ * defines its outcome without monotonicity: what is returned always fits max_bytes and is what that rule chooses among the
+ * tolerances probed; it is not claimed to be the tightest tolerance that fits.
+ * Errors (NULL and a message): a null report, eps_hi or rounds as for BuildCorrectionWithinBytes (found before the volume is looked
+ * at); those of CorrectionRates and BuildCorrectionPacked; eps_hi that does not fit (max_bytes, eps_hi and the size are named). */
+typedef struct vnrAmdCorrectionRateCoded {
+  vnrAmdCorrectionRate rate;            /* exactly what CorrectionRates gives for this tolerance */
+  uint64_t coded_stream_words,          /* sum over the flagged cells of the 64-bit words of the cell's stream */
+           coded_payload_bytes,         /* pad8(4 n_flagged) + 8 coded_stream_words */
+           coded_serialized_bytes;      /* 104 + 8 n_flagged + coded_payload_bytes: the size of SerializeCoded */
+} vnrAmdCorrectionRateCoded;            /* 96 bytes */
+int vnrAmdNeuralVolumeCorrectionRatesCoded(vnrAmdVolume neural, const void* d_ref, int value_type, const int64_t strides[3],
+                                           float range_lo, float range_hi, const double* eps, int n_eps, void* stream,
+                                           vnrAmdCorrectionRateCoded* out /* host, n_eps entries */);
+#define VNR_AMD_CORRECTION_FORM_CODED 2  /* names the form; BuildCorrectionWithinBytes still refuses it */
+vnrAmdCorrection vnrAmdNeuralVolumeBuildCorrectionCodedWithinBytes(vnrAmdVolume neural, const void* d_ref, int value_type,
+    const int64_t strides[3], float range_lo, float range_hi, uint64_t max_bytes, double eps_hi, int rounds,
     void* stream, vnrAmdCorrectionBudget* report);
 /* AMD extension: corrections built straight into bit planes.  BuildCorrectionPacked is BuildCorrection (arguments, validation,
  * refusals and messages, the refusal of a code wider than 32 bits included; a refused call returns NULL and keeps nothing
@@ -539,8 +582,8 @@ int  vnrAmdCorrectionSerializePackedToDevice(vnrAmdCorrection, void* d_bytes, si
  * holds nothing on the device (read from bytes of any form and never applied, or without a flagged cell) is transcoded on the host.
  * SerializeCodedToDevice writes the same bytes into device memory, encoded straight into the destination; its arguments, its
  * size-only call (d_bytes == NULL) and its refusals are SerializePackedToDevice's.
- * Not built: the rate call and BuildCorrectionWithinBytes do not know the coded form (vnrAmdCorrectionRate's layout is ABI); there is
- * no apply straight from coded streams; there is no prediction across voxels.
+ * Byte budgets in this form: CorrectionRatesCoded and BuildCorrectionCodedWithinBytes above.
+ * Not built: there is no apply straight from coded streams; there is no prediction across voxels.
  * Errors: a null handle, result or bytes; capacity < *size (both are named, nothing is written); malformed bytes, each rule by name. */
 int  vnrAmdCorrectionSerializeCoded(vnrAmdCorrection, void** bytes, size_t* size);
 vnrAmdCorrection vnrAmdCreateCorrectionFromCodedBytes(const void* bytes, size_t size);

@@ -79,6 +79,10 @@ class CorrectionRate(C.Structure):
                 ("packed_serialized_bytes", C.c_uint64)]
 
 
+class CorrectionRateCoded(C.Structure):
+    _fields_ = [("rate", CorrectionRate), ("coded_stream_words", C.c_uint64), ("coded_payload_bytes", C.c_uint64), ("coded_serialized_bytes", C.c_uint64)]
+
+
 class CorrectionBudget(C.Structure):
     _fields_ = [("eps", C.c_double), ("bytes", C.c_uint64), ("eps_tighter", C.c_double), ("bytes_tighter", C.c_uint64), ("rate_passes", C.c_int)]
 
@@ -287,6 +291,8 @@ def lib():
     sig("vnrAmdReleaseCorrection", None, P)
     sig("vnrAmdNeuralVolumeCorrectionRates", I, P, P, I, I64P, F, F, C.POINTER(D), I, P, C.POINTER(CorrectionRate))
     sig("vnrAmdNeuralVolumeBuildCorrectionWithinBytes", P, P, P, I, I64P, F, F, U64, I, D, I, P, C.POINTER(CorrectionBudget))
+    sig("vnrAmdNeuralVolumeCorrectionRatesCoded", I, P, P, I, I64P, F, F, C.POINTER(D), I, P, C.POINTER(CorrectionRateCoded))
+    sig("vnrAmdNeuralVolumeBuildCorrectionCodedWithinBytes", P, P, P, I, I64P, F, F, U64, D, I, P, C.POINTER(CorrectionBudget))
     sig("vnrAmdNeuralVolumeBuildCorrectionPacked", P, P, P, I, I64P, F, F, D, P)
     sig("vnrAmdCorrectionSerializePackedToDevice", I, P, P, SZ, C.POINTER(SZ), P)
     sig("vnrAmdCorrectionSerializeCoded", I, P, C.POINTER(P), C.POINTER(SZ))

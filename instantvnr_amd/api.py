@@ -636,10 +636,11 @@ def vnrNeuralVolumeBuildCorrectionPacked(v, d_ref, dtype, eps, strides=None, val
     return Correction(lib().vnrAmdNeuralVolumeBuildCorrectionPacked(v.h, p, t, s, lo, hi, float(eps), st))
 
 
-def vnrNeuralVolumeCorrectionRates(v, d_ref, dtype, tolerances, strides=None, value_range=None, stream=None):
+def vnrNeuralVolumeCorrectionRates(v, d_ref, dtype, tolerances, strides=None, value_range=None, stream=None, coded=False):
     """what vnrNeuralVolumeBuildCorrection would cost at each of 1 .. 64 `tolerances`, exactly, from one evaluation of the network and
     without building anything (include/vnr_amd.h, "corrections to a byte budget") -> a list of dicts of vnrAmdCorrectionRate, one a
-    tolerance, in their order; `refused` as bool"""
+    tolerance, in their order; `refused` as bool.  coded: vnrAmdNeuralVolumeCorrectionRatesCoded, the same dicts with the coded
+    form's coded_stream_words, coded_payload_bytes and coded_serialized_bytes beside the rest"""
     p, _, t, s, _, _, st = _device_source_args(d_ref, dtype, strides, None, stream)
     lo, hi = _round_trip_range(np.dtype(dtype), value_range)
     try:
@@ -648,29 +649,44 @@ def vnrNeuralVolumeCorrectionRates(v, d_ref, dtype, tolerances, strides=None, va
         raise VnrAmdError(f"tolerances must be 1 to 64 numbers, got {tolerances!r}") from None
     if not 1 <= len(tol) <= 64:
         raise VnrAmdError(f"tolerances must be 1 to 64 numbers, got {len(tol)}")
-    out = (_lib.CorrectionRate * len(tol))()
-    check(lib().vnrAmdNeuralVolumeCorrectionRates(v.h, p, t, s, lo, hi, (C.c_double * len(tol))(*tol), len(tol), st, out))
-    rates = [{k: getattr(e, k) for k, _ in _lib.CorrectionRate._fields_} for e in out]
+    eps = (C.c_double * len(tol))(*tol)
+    if coded:
+        out = (_lib.CorrectionRateCoded * len(tol))()
+        check(lib().vnrAmdNeuralVolumeCorrectionRatesCoded(v.h, p, t, s, lo, hi, eps, len(tol), st, out))
+        rates = [{**{k: getattr(e.rate, k) for k, _ in _lib.CorrectionRate._fields_}, **{k: getattr(e, k) for k, _ in _lib.CorrectionRateCoded._fields_[1:]}}
+                 for e in out]
+    else:
+        out = (_lib.CorrectionRate * len(tol))()
+        check(lib().vnrAmdNeuralVolumeCorrectionRates(v.h, p, t, s, lo, hi, eps, len(tol), st, out))
+        rates = [{k: getattr(e, k) for k, _ in _lib.CorrectionRate._fields_} for e in out]
     for r in rates:
         r["refused"] = bool(r["refused"])
     return rates
 
 
-CORRECTION_FORMS = {"fixed": 0, "packed": 1}
+CORRECTION_FORMS = {"fixed": 0, "packed": 1}       # what vnrAmdNeuralVolumeBuildCorrectionWithinBytes takes
+CORRECTION_FORM_CODED = 2                           # VNR_AMD_CORRECTION_FORM_CODED: the form of the entry point of its own
 
 
 def vnrNeuralVolumeBuildCorrectionWithinBytes(v, d_ref, dtype, max_bytes, eps_hi, form="packed", rounds=2, strides=None, value_range=None, stream=None):
     """vnrNeuralVolumeBuildCorrection at the tightest tolerance <= eps_hi the search finds whose serialised size in `form` ("fixed":
     to_bytes, "packed": to_packed_bytes) is at most max_bytes; `rounds` refinements after the ladder eps_hi * 2^-j.
+    form "coded": vnrAmdNeuralVolumeBuildCorrectionCodedWithinBytes, the size of to_coded_bytes; the correction is built straight
+    into the packed resident form and its coded bytes are cached.  Coded sizes can grow with the tolerance: what comes back always
+    fits and is what the search's rule chooses, not provably the tightest tolerance that fits.
     -> (Correction, dict(eps, bytes, eps_tighter, bytes_tighter, rate_passes))"""
     p, _, t, s, _, _, st = _device_source_args(d_ref, dtype, strides, None, stream)
     lo, hi = _round_trip_range(np.dtype(dtype), value_range)
-    if form not in CORRECTION_FORMS:
-        raise VnrAmdError(f"form must be 'fixed' or 'packed', got {form!r}")
+    if form != "coded" and form not in CORRECTION_FORMS:
+        raise VnrAmdError(f"form must be 'fixed', 'packed' or 'coded', got {form!r}")
     if int(max_bytes) < 0:
         raise VnrAmdError(f"max_bytes must be a byte count >= 0, got {max_bytes!r}")
     e = _lib.CorrectionBudget()
-    h = lib().vnrAmdNeuralVolumeBuildCorrectionWithinBytes(v.h, p, t, s, lo, hi, int(max_bytes), CORRECTION_FORMS[form], float(eps_hi), int(rounds), st, C.byref(e))
+    if form == "coded":
+        h = lib().vnrAmdNeuralVolumeBuildCorrectionCodedWithinBytes(v.h, p, t, s, lo, hi, int(max_bytes), float(eps_hi), int(rounds), st, C.byref(e))
+    else:
+        h = lib().vnrAmdNeuralVolumeBuildCorrectionWithinBytes(v.h, p, t, s, lo, hi, int(max_bytes), CORRECTION_FORMS[form], float(eps_hi), int(rounds), st,
+                                                              C.byref(e))
     c = Correction(h)
     return c, {k: getattr(e, k) for k, _ in _lib.CorrectionBudget._fields_}
 

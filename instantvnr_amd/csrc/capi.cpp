@@ -666,6 +666,50 @@ vnrAmdCorrection vnrAmdNeuralVolumeBuildCorrectionWithinBytes(vnrAmdVolume v, co
     return new vnrAmdCorrection_t{std::move(corr)};
   });
 }
+int vnrAmdNeuralVolumeCorrectionRatesCoded(vnrAmdVolume v, const void* d_ref, int value_type, const int64_t strides[3], float range_lo, float range_hi,
+                                           const double* eps, int n_eps, void* stream, vnrAmdCorrectionRateCoded* out)
+{
+  static_assert(sizeof(vnrAmdCorrectionRateCoded) == sizeof(CorrectionRateCoded) && sizeof(CorrectionRateCoded) == 96 &&
+                    offsetof(vnrAmdCorrectionRateCoded, coded_stream_words) == sizeof(vnrAmdCorrectionRate),
+                "vnrAmdCorrectionRateCoded and vnr::CorrectionRateCoded are one layout");
+  return guarded([&]() {
+    CorrectionRateCoded* o = reinterpret_cast<CorrectionRateCoded*>(out);
+    correction_rates_check(eps, n_eps, o ? &o->rate : nullptr);   // (what needs no volume comes first)
+    as_neural(v)->correction_rates_coded(DeviceSource{d_ref, value_type, strides, (hipStream_t)stream}, range_lo, range_hi, eps, n_eps, o);
+  });
+}
+vnrAmdCorrection vnrAmdNeuralVolumeBuildCorrectionCodedWithinBytes(vnrAmdVolume v, const void* d_ref, int value_type, const int64_t strides[3], float range_lo,
+                                                                   float range_hi, uint64_t max_bytes, double eps_hi, int rounds, void* stream,
+                                                                   vnrAmdCorrectionBudget* report)
+{
+  return guarded_new<vnrAmdCorrection_t>([&]() {
+    if (!report) throw std::runtime_error("null result");
+    correction_budget_check(eps_hi, rounds);
+    NeuralVolume* n = as_neural(v);
+    const DeviceSource ref{d_ref, value_type, strides, (hipStream_t)stream};
+    const CorrectionBudgetResult r = correction_budget_search(
+        [&](const double* eps, int n_eps, uint64_t* bytes, int* refused) {
+          CorrectionRateCoded rates[kCorrectionBudgetLadder];
+          n->correction_rates_coded(ref, range_lo, range_hi, eps, n_eps, rates);
+          for (int k = 0; k < n_eps; ++k) {
+            bytes[k] = rates[k].coded_serialized_bytes;
+            refused[k] = rates[k].rate.refused;
+          }
+        },
+        max_bytes, eps_hi, rounds);
+    // the direct build: the planes and their index, no fixed-width payload; then the device encode, once, cached for SerializeCoded
+    std::shared_ptr<Correction> corr = n->build_correction_packed(ref, range_lo, range_hi, r.eps);
+    const uint64_t built = kCorrectionHeaderBytes + 8 * corr->data.cells.size() + correction_coded_payload(*corr, Runtime::get().stream).size();
+    if (built != r.bytes) {
+      char e[40];
+      std::snprintf(e, sizeof(e), "%.17g", r.eps);
+      throw std::runtime_error(std::string("internal error: the correction built at eps ") + e + " has " + std::to_string(built) +
+                               " serialised bytes in the coded form, the rate pass gave " + std::to_string(r.bytes));
+    }
+    *report = vnrAmdCorrectionBudget{r.eps, r.bytes, r.eps_tighter, r.bytes_tighter, r.rate_passes};
+    return new vnrAmdCorrection_t{std::move(corr)};
+  });
+}
 int vnrAmdCorrectionGetInfo(vnrAmdCorrection c, vnrAmdCorrectionInfo* out)
 {
   return guarded([&]() {

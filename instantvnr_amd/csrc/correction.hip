@@ -12,6 +12,8 @@
 // correction_rates ("corrections to a byte budget") answers what many tolerances would cost without building any: one chunked
 // evaluation in the packed form's order, a wave per group of 64 codes, the build's quantise per tolerance, wave reductions and
 // integer atomics per cell; tests/correction_rate_ref.py restates it.  The search on top of it is correction_budget.cpp, host only.
+// correction_rates_coded ("byte budgets in the coded form") is the same pass with the coded instantiation of both kernels, which adds
+// the exact size of the coded form per tolerance; tests/correction_coded_rate_ref.py restates that.
 //
 // build_correction_packed ("corrections built straight into bit planes", at the end of this file) gives build_correction's correction
 // in the packed resident form without the fixed-width codes in between: the rate pass's walk for one tolerance with the error reports
@@ -514,16 +516,38 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t v)
   return v;
 }
 
+// the arguments a kernel takes only in its coded instantiation, by place
+template <typename A, typename... R> __device__ __forceinline__ A first_of(A a, R...) { return a; }
+template <typename A, typename B, typename... R> __device__ __forceinline__ B second_of(A, B b, R...) { return b; }
+
+// what a plane of the coded form costs: a list of its c <= 9 set lanes, or one bit and the plane (correction_coded_format.h)
+__device__ __forceinline__ uint32_t coded_plane_bits(uint64_t plane)
+{
+  const uint32_t count = (uint32_t)__popcll(plane);
+  return count <= kCodedListMax ? 5u + 6u * count : 65u;
+}
+
 // groups [g0, g0 + n_groups) of the walk, their values in values[64 * (group - g0) + lane].  A lane reads its voxel of ref through the
 // strides, converts its value and forms the code of every tolerance of the batch with the build's quantise; per tolerance the wave
 // reduces max |q| and the bit length of the largest z (the group's nbits) and counts the codes != 0 with a ballot.  Lane 0 folds the
 // two maxima into the cell's pair (a cell has up to 64 groups, which may lie in several blocks and chunks) and the count into the
 // block's; all three are integers, so the result is exact whatever the order.  stats[j * n_cells + cell], nonzero[j]: of tolerance j.
-template <typename T>
+//
+// Coded (the coded rate call alone; the plain call's kernel is the instantiation without it and takes no argument for it): the length
+// of the group's record of the coded form (correction_coded_format.h) in closed form, as correction_code_measure_kernel finds it from
+// the resident codes.  The magnitude of a lane is |q| (kind 2: ref's bit pattern), mbits the bit length of the wave's largest; a plane
+// is one ballot and one popcount and costs 5 + 6 c bits as a list of c <= 9 lanes, 65 dense; kinds 0 and 1 add a sign bit per lane
+// with q != 0, the ballot that is there already.  All of it is wave-uniform, the plane loop a scalar loop.  Lane 0 adds the sum to
+// coded_bits[j * n_cells + cell]: one integer atomic, exact in any order.  The 7 bits of mbits are not in it: EVERY group of a
+// flagged cell has them, the groups of zeros that leave above included, and correction_rate_final_kernel adds them per cell.  A cell
+// has at most 64 groups of at most 64 planes and 64 signs, so its sum stays below 2^19.  A magnitude is read from aq, which
+// saturates at 2^32 - 1: such an entry is refused and its sizes are never reported.
+template <typename T, typename... Coded>
 __global__ void __launch_bounds__(kBlock) correction_rate_kernel(const T* __restrict__ ref, int64_t sx, int64_t sy, int64_t sz, GroupWalk w, uint64_t g0, uint32_t n_groups,
                                                                  const float* __restrict__ values, Conversion c, RateBatch batch, uint64_t n_cells,
-                                                                 RateCell* __restrict__ stats, unsigned long long* __restrict__ nonzero)
+                                                                 RateCell* __restrict__ stats, unsigned long long* __restrict__ nonzero, Coded... coded)
 {
+  constexpr bool kCoded = sizeof...(Coded) != 0;   // coded: (uint32_t* coded_bits), beside stats and zeroed by the caller
   __shared__ uint32_t block_nonzero[kRateBatch];   // (a chunk holds at most 2^28 samples)
   if (threadIdx.x < kRateBatch) block_nonzero[threadIdx.x] = 0;
   __syncthreads();
@@ -556,6 +580,22 @@ __global__ void __launch_bounds__(kBlock) correction_rate_kernel(const T* __rest
         if (nbits) atomicAdd(&s->nbits, nbits);
         if (differ) atomicAdd(&block_nonzero[j], (uint32_t)__popcll(differ));
       }
+      if constexpr (kCoded) {
+        uint32_t* __restrict__ coded_bits = first_of(coded...);
+        uint32_t mbits, bits;
+        bool verbatim = false;
+        if constexpr (std::is_floating_point_v<T>) verbatim = k.kind == kCorrectionVerbatim;
+        if (verbatim) {   // the planes of the patterns are the planes of z; no signs
+          mbits = (uint32_t)__builtin_amdgcn_readfirstlane((int)nbits);
+          bits = 0;
+          for (uint32_t b = 0; b < mbits; ++b) bits += coded_plane_bits(__ballot((int)((z >> b) & 1)));
+        } else {
+          mbits = (uint32_t)__builtin_amdgcn_readfirstlane((int)(m ? 32u - (uint32_t)__clz((int)m) : 0u));
+          bits = (uint32_t)__popcll(differ);
+          for (uint32_t b = 0; b < mbits; ++b) bits += coded_plane_bits(__ballot((int)((aq >> b) & 1u)));
+        }
+        if (lane == 0 && bits) atomicAdd(coded_bits + ((uint64_t)j * n_cells + p.cell), bits);
+      }
     }
   }
   __syncthreads();
@@ -577,13 +617,18 @@ __device__ __forceinline__ uint64_t block_sum(uint64_t v)
   return r;
 }
 
-// block j: the per-cell pairs of tolerance j -> its sums, with the header's width rule and the paddings of both serialised forms
+// block j: the per-cell pairs of tolerance j -> its sums, with the header's width rule and the paddings of both serialised forms.
+// Coded: a flagged cell's stream is its records' bits, 7 for every group's mbits plus what the rate kernel summed, filled up to whole
+// 64-bit words; coded_words[j] gets the sum over the flagged cells.
+template <typename... Coded>
 __global__ void __launch_bounds__(kBlock) correction_rate_final_kernel(const RateCell* __restrict__ stats, uint64_t n_cells, CellGrid g, RateWidths widths,
-                                                                       const unsigned long long* __restrict__ nonzero, RateSums* __restrict__ out)
+                                                                       const unsigned long long* __restrict__ nonzero, RateSums* __restrict__ out, Coded... coded)
 {
+  constexpr bool kCoded = sizeof...(Coded) != 0;   // coded: (const uint32_t* coded_bits, uint64_t* coded_words)
   const uint32_t j = blockIdx.x;
   const uint32_t verbatim = widths.verbatim[j];
   uint64_t n_flagged = 0, n_groups = 0, payload = 0, nbits = 0, refused = 0;
+  [[maybe_unused]] uint64_t words = 0;
   for (uint64_t cl = threadIdx.x; cl < n_cells; cl += kBlock) {
     const RateCell s = stats[(uint64_t)j * n_cells + cl];
     if (s.max_q == 0) continue;
@@ -595,9 +640,14 @@ __global__ void __launch_bounds__(kBlock) correction_rate_final_kernel(const Rat
     n_groups += (voxels + 63) / 64;
     payload += (voxels * width + 15) / 16 * 16;
     nbits += s.nbits;
+    if constexpr (kCoded) words += ((uint64_t)first_of(coded...)[(uint64_t)j * n_cells + cl] + 7 * ((voxels + 63) / 64) + 63) / 64;
   }
   n_flagged = block_sum(n_flagged); n_groups = block_sum(n_groups); payload = block_sum(payload); nbits = block_sum(nbits); refused = block_sum(refused);
   if (threadIdx.x == 0) out[j] = RateSums{n_flagged, n_groups, payload, nbits, nonzero[j], refused};
+  if constexpr (kCoded) {
+    words = block_sum(words);
+    if (threadIdx.x == 0) second_of(coded...)[j] = words;
+  }
 }
 
 Quantiser make_quantiser(uint32_t kind, double eps)
@@ -786,6 +836,32 @@ void NeuralVolume::correction_rates(const DeviceSource& ref, float range_lo, flo
 {
   if (!net_.valid()) throw std::runtime_error("neural volume has no valid network");
   correction_rates_check(eps, n_eps, out);
+  rate_pass(ref, range_lo, range_hi, eps, n_eps, out, nullptr);
+}
+
+void NeuralVolume::correction_rates_coded(const DeviceSource& ref, float range_lo, float range_hi, const double* eps, int n_eps, CorrectionRateCoded* out)
+{
+  if (!net_.valid()) throw std::runtime_error("neural volume has no valid network");
+  correction_rates_check(eps, n_eps, out ? &out->rate : nullptr);
+  CorrectionRate rates[kCorrectionMaxRates];
+  uint64_t words[kCorrectionMaxRates];
+  rate_pass(ref, range_lo, range_hi, eps, n_eps, rates, words);
+  for (int j = 0; j < n_eps; ++j) {
+    CorrectionRateCoded r{rates[j], 0, 0, 0};
+    if (!r.rate.refused) {
+      r.coded_stream_words = words[j];
+      r.coded_payload_bytes = correction_coded_table_bytes(r.rate.n_flagged) + 8 * words[j];
+      r.coded_serialized_bytes = kCorrectionHeaderBytes + 8 * r.rate.n_flagged + r.coded_payload_bytes;
+    }
+    out[j] = r;
+  }
+}
+
+// the rate pass of both calls.  coded_words null: the plain call, with the kernels, the scratch and the launches it always had;
+// otherwise the coded variants of both kernels, 4 more bytes of scratch per macrocell and tolerance, and coded_words[j] = the
+// 64-bit words of all streams of tolerance j (whatever it is where the entry is refused)
+void NeuralVolume::rate_pass(const DeviceSource& ref, float range_lo, float range_hi, const double* eps, int n_eps, CorrectionRate* out, uint64_t* coded_words)
+{
   const vec3i grid = desc.dims;
   vec3i lower;
   const BoxLayout L = validate_box_array(ref.data, ref.type, ref.strides, nullptr, nullptr, grid, lower, range_lo, range_hi);
@@ -817,10 +893,17 @@ void NeuralVolume::correction_rates(const DeviceSource& ref, float range_lo, flo
   stats.resize(n_cells * (uint64_t)n_eps);
   nonzero.resize(n_eps);
   sums.resize(n_eps);
+  DeviceBuffer<uint32_t> coded_bits(MemTag::Network);   // the coded call alone: a cell's record bits beyond the 7 of every group
+  DeviceBuffer<uint64_t> d_coded_words(MemTag::Network);
+  if (coded_words) {
+    coded_bits.resize(n_cells * (uint64_t)n_eps);
+    d_coded_words.resize(n_eps);
+  }
   EventGuard ev;
   wait_for(ref.producer, stream, ev);
   stats.zero(stream);
   nonzero.zero(stream);
+  if (coded_words) coded_bits.zero(stream);
   const uint32_t max_blocks = (uint32_t)Runtime::get().n_cus * 8;
   for (uint64_t g0 = 0; g0 < w.n_groups; g0 += chunk_groups) {
     const uint32_t n_groups = (uint32_t)std::min(chunk_groups, w.n_groups - g0), n = 64 * n_groups;
@@ -834,14 +917,26 @@ void NeuralVolume::correction_rates(const DeviceSource& ref, float range_lo, flo
       for (int j = 0; j < batch.n; ++j) batch.k[j] = quantisers[j0 + j];
       dispatch_type(ref.type, [&](auto* tag) {
         using T = std::remove_pointer_t<decltype(tag)>;
-        correction_rate_kernel<T><<<blocks, kBlock, 0, stream>>>((const T*)ref.data, sx, sy, sz, w, g0, n_groups, dd_values_.ptr, c, batch, n_cells,
-                                                                 stats.ptr + (uint64_t)j0 * n_cells, nonzero.ptr + j0);
+        if (coded_words)
+          correction_rate_kernel<T, uint32_t*><<<blocks, kBlock, 0, stream>>>((const T*)ref.data, sx, sy, sz, w, g0, n_groups, dd_values_.ptr, c, batch, n_cells,
+                                                                              stats.ptr + (uint64_t)j0 * n_cells, nonzero.ptr + j0,
+                                                                              coded_bits.ptr + (uint64_t)j0 * n_cells);
+        else
+          correction_rate_kernel<T><<<blocks, kBlock, 0, stream>>>((const T*)ref.data, sx, sy, sz, w, g0, n_groups, dd_values_.ptr, c, batch, n_cells,
+                                                                   stats.ptr + (uint64_t)j0 * n_cells, nonzero.ptr + j0);
       });
       VNR_HIP_CHECK(hipGetLastError());
     }
   }
-  correction_rate_final_kernel<<<n_eps, kBlock, 0, stream>>>(stats.ptr, n_cells, g, widths, nonzero.ptr, sums.ptr);
-  VNR_HIP_CHECK(hipGetLastError());
+  if (coded_words) {
+    correction_rate_final_kernel<const uint32_t*, uint64_t*><<<n_eps, kBlock, 0, stream>>>(stats.ptr, n_cells, g, widths, nonzero.ptr, sums.ptr, coded_bits.ptr,
+                                                                                             d_coded_words.ptr);
+    VNR_HIP_CHECK(hipGetLastError());
+    VNR_HIP_CHECK(hipMemcpyAsync(coded_words, d_coded_words.ptr, n_eps * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+  } else {
+    correction_rate_final_kernel<><<<n_eps, kBlock, 0, stream>>>(stats.ptr, n_cells, g, widths, nonzero.ptr, sums.ptr);
+    VNR_HIP_CHECK(hipGetLastError());
+  }
   std::vector<RateSums> host(n_eps);
   sums.download(host.data(), n_eps, stream);   // (synchronises)
   for (int j = 0; j < n_eps; ++j) {

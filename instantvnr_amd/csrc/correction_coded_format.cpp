@@ -155,6 +155,23 @@ std::vector<uint8_t> coded_payload(const std::vector<uint32_t>& cell_words, cons
 
 }  // namespace
 
+uint32_t correction_coded_record_bits(const uint64_t m[kCorrectionGroup], uint32_t kind)
+{
+  uint64_t any = 0;
+  uint32_t nonzero = 0;
+  for (uint32_t l = 0; l < kCorrectionGroup; ++l) {
+    any |= m[l];
+    nonzero += m[l] != 0;
+  }
+  uint32_t bits = 7;
+  for (uint32_t b = 0; b < bit_length(any); ++b) {
+    uint32_t c = 0;
+    for (uint32_t l = 0; l < kCorrectionGroup; ++l) c += (uint32_t)((m[l] >> b) & 1);
+    bits += c <= kCodedListMax ? 5 + 6 * c : 65;
+  }
+  return kind == kCorrectionVerbatim ? bits : bits + nonzero;
+}
+
 std::vector<uint8_t> correction_coded_write(const CorrectionHeader& h, const std::vector<CorrectionCellEntry>& cells, const std::vector<uint8_t>& payload)
 {
   std::vector<uint8_t> out;

@@ -36,6 +36,13 @@ struct CorrectionCoded {
 
 inline uint64_t correction_coded_table_bytes(uint64_t n_flagged) { return (4 * n_flagged + 7) / 8 * 8; }
 
+// The bits of a group's record in closed form, from the magnitudes m_l of its 64 lanes (kind 2: the patterns; lanes beyond the cell's
+// voxels 0) and the kind: 7, then 5 + 6 c or 65 for each plane below the bit length of the largest m_l by its count c, then (kinds 0
+// and 1) a bit per m_l != 0.  A cell's stream is ceil(the sum over its groups / 64) words.  This is what the rate pass of
+// correction.hip and the encoder of correction_code.hip count on the device; nothing on the device calls it, it is here to be held
+// to what the writer below really writes.
+uint32_t correction_coded_record_bits(const uint64_t m[kCorrectionGroup], uint32_t kind);
+
 std::vector<uint8_t> correction_coded_write(const CorrectionHeader& h, const std::vector<CorrectionCellEntry>& cells, const std::vector<uint8_t>& payload);
 // throws std::runtime_error("malformed coded correction bytes: <rule>"); everything is validated before anything is allocated by the
 // bytes' say

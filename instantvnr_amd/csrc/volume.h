@@ -200,6 +200,11 @@ struct CorrectionRate {
   int kind, refused;
   uint64_t n_flagged, n_voxels_flagged, n_groups, payload_bytes, serialized_bytes, packed_payload_bytes, packed_serialized_bytes;
 };
+// vnrAmdCorrectionRateCoded, field for field: the entry above and what SerializeCoded of that build would give
+struct CorrectionRateCoded {
+  CorrectionRate rate;
+  uint64_t coded_stream_words, coded_payload_bytes, coded_serialized_bytes;
+};
 constexpr int kCorrectionMaxRates = 64;
 // what a rate call refuses before it looks at the volume: a null eps or out, n_eps outside 1 .. 64, an eps[k] that is negative, NaN or infinite
 void correction_rates_check(const double* eps, int n_eps, const CorrectionRate* out);
@@ -368,6 +373,10 @@ public:
   // build_correction(ref, range, eps[k]) would give, from ONE chunked evaluation of the network; nothing is built, `ref` is only read,
   // and only the n_eps results cross to the host (out: host memory).
   void correction_rates(const DeviceSource& ref, float range_lo, float range_hi, const double* eps, int n_eps, CorrectionRate* out);
+  // correction_rates_coded: correction_rates' entries bit for bit, each with the exact size of the coded form beside it; the same one
+  // evaluation, with the coded variants of the rate kernels (a ballot and a popcount per plane, 4 more bytes of scratch per macrocell
+  // and tolerance).  correction_rates itself runs what it always ran.
+  void correction_rates_coded(const DeviceSource& ref, float range_lo, float range_hi, const double* eps, int n_eps, CorrectionRateCoded* out);
   uint64_t params_hash();   // FNV-1a 64 of the fp16 parameter blob
   // network.cu:328-365 / :367-405: raw fp32, z-slice by z-slice, every slice padded to a multiple of 256 values
   void save_inference_volume(const std::string& filename);
@@ -382,6 +391,7 @@ public:
   hipStream_t stream;
 
 private:
+  void rate_pass(const DeviceSource& ref, float range_lo, float range_hi, const double* eps, int n_eps, CorrectionRate* out, uint64_t* coded_words);
   SimpleVolume* source_ = nullptr;
   std::shared_ptr<void> source_keepalive_;
   Network net_;

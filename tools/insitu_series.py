@@ -53,7 +53,10 @@ ingest time are printed.
                          eps and its bytes, the tolerance just below that did not fit and its bytes, the compressed bytes (params.json
                          plus the correction) and the ratio, max_abs_after, the rate passes; the whole call timed, beside one rate call
                          of 16 tolerances (vnrAmdNeuralVolumeCorrectionRates)
-  --budget-form FORM     with --byte-budget: fixed | packed, the serialised form BYTES bounds                     [packed]
+  --budget-form FORM     with --byte-budget: fixed | packed | coded, the serialised form BYTES bounds             [packed]
+                         coded: vnrAmdNeuralVolumeBuildCorrectionCodedWithinBytes, whose correction is built straight into the bit
+                         planes and stored as to_coded_bytes(); the rate call timed is vnrAmdNeuralVolumeCorrectionRatesCoded, beside
+                         the plain one, and the packed size at the chosen tolerance is reported next to the coded one
   --budget-rounds N      with --byte-budget: refinement rounds after the ladder eps_hi * 2^-j, 0 .. 8             [2]
   --guided               error-guided batches instead of the series (vnrAmdNeuralVolumeGuideSamplingByError): ONE static field, the
                          synthetic blob field with plateaus at both ends, trained --steps-per-frame steps in all, twice with the same
@@ -107,7 +110,10 @@ voxels alone and applies the correction in the resident form, "roi_plain_decode"
 The --byte-budget times are host clocks around whole calls, each warmed up once: "budget_ms" is the whole
 vnrAmdNeuralVolumeBuildCorrectionWithinBytes (1 + rounds rate passes at most, one build, for the packed form the device pack),
 "rate_pass_ms" one vnrAmdNeuralVolumeCorrectionRates call over the ladder's 16 tolerances: one evaluation of the network.  The
-kernels are correction_rate_coords_kernel, correction_rate_kernel and correction_rate_final_kernel."""
+kernels are correction_rate_coords_kernel, correction_rate_kernel and correction_rate_final_kernel.  With --budget-form coded the call
+is vnrAmdNeuralVolumeBuildCorrectionCodedWithinBytes (the coded rate passes, the direct build, the device encode), "rate_pass_ms" is
+one vnrAmdNeuralVolumeCorrectionRatesCoded call (correction_rate_coded_kernel, correction_rate_final_coded_kernel) and
+"plain_rate_pass_ms" one vnrAmdNeuralVolumeCorrectionRates call, alternating."""
 import argparse
 import json
 import os
@@ -364,13 +370,26 @@ def byte_budget(neural, ptr, dtype, strides, dims, value_range, max_bytes, form,
     except api.VnrAmdError as e:      # not even eps_hi fits
         row["budget_refused"] = str(e)
         return row
-    blob = corr.to_packed_bytes() if form == "packed" else corr.to_bytes()
+    blob = corr.to_coded_bytes() if form == "coded" else (corr.to_packed_bytes() if form == "packed" else corr.to_bytes())      # what is stored
     row.update(budget_eps=rep["eps"], budget_bytes=rep["bytes"], serialized_equals_report=len(blob) == rep["bytes"], eps_tighter=rep["eps_tighter"],
                bytes_tighter=rep["bytes_tighter"], rate_passes=rep["rate_passes"], compressed_bytes=n_params + rep["bytes"],
                ratio=round(raw / (n_params + rep["bytes"]), 3), max_abs_after=corr.info()["max_abs_after"], budget_ms=round(best, 4),
                budget_median_ms=round(median, 4))
     corr.release()
     ladder = [eps_hi * 2.0 ** -j for j in range(16)]
+    if form == "coded":      # the coded rate call beside the plain one, alternating; and what the packed form needs at the chosen tolerance
+        at = api.vnrNeuralVolumeCorrectionRates(neural, ptr, dtype, [rep["eps"]], strides, value_range, coded=True)[0]
+        row.update(rate_equals_report=at["coded_serialized_bytes"] == rep["bytes"], packed_bytes_at_budget_eps=at["packed_serialized_bytes"])
+        samples = {True: [], False: []}
+        for i in range(2 * (max(repeat, 10) + 1)):
+            coded = i % 2 == 0
+            t0 = time.perf_counter()
+            api.vnrNeuralVolumeCorrectionRates(neural, ptr, dtype, ladder, strides, value_range, coded=coded)
+            if i >= 2:      # (one warm-up each)
+                samples[coded].append((time.perf_counter() - t0) * 1e3)
+        row.update(rate_pass_ms=round(min(samples[True]), 4), rate_pass_median_ms=round(statistics.median(samples[True]), 4),
+                   plain_rate_pass_ms=round(min(samples[False]), 4), plain_rate_pass_median_ms=round(statistics.median(samples[False]), 4))
+        return row
     _, best, median = timed(lambda: api.vnrNeuralVolumeCorrectionRates(neural, ptr, dtype, ladder, strides, value_range), repeat, 1)
     row.update(rate_pass_ms=round(best, 4), rate_pass_median_ms=round(median, 4))
     return row
@@ -437,7 +456,7 @@ def main(argv=None):
     p.add_argument("--resident", default="fixed", choices=["fixed", "packed"])
     p.add_argument("--roi", default=None, metavar="x0,y0,z0,sx,sy,sz")
     p.add_argument("--byte-budget", type=int, default=None, metavar="BYTES")
-    p.add_argument("--budget-form", default="packed", choices=["fixed", "packed"])
+    p.add_argument("--budget-form", default="packed", choices=["fixed", "packed", "coded"])
     p.add_argument("--budget-rounds", type=int, default=2, metavar="N")
     p.add_argument("--guided", action="store_true")
     p.add_argument("--uniform-fraction", type=float, default=0.25)

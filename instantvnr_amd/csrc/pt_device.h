@@ -69,12 +69,76 @@ struct PtRay {
   }
 };
 
+// ---- the path tracer's two transcendental functions, restated -------------------------------------------------------------------
+// A free path is -log(1 - u) / majorant and a bounce's direction is sincos(2 pi u): libm's last bit moves the tentative collision by
+// an ulp of t, and on a neural volume that is not harmless: a multiresolution grid multiplies the ulp of the coordinate by its
+// resolution, some fp16 feature rounds the other way and the pixel changes by 1e-4 .. 1e-3 on the SAME path.  The device library's
+// logf differs from glibc's in the last bit on 39 % of the 2^24 random numbers (its sincosf on 33 %), so frames followed the oracle's
+// (which calls glibc) on 0.95 .. 0.99 of the pixels only, and would move with every change of the device library.  These are the
+// algorithms glibc has used since 2.27 / 2.28 (S. Nagy's logf and sincosf of Arm's optimized-routines: a table step, then a short
+// polynomial in double, rounded to float once), written for the arguments the path tracer has: x = 1 - u in [2^-24, 1] and
+// phi = 2 pi u in [0, 2 pi].  In double every operation is exact enough that contraction does not matter; on all 2^24 random numbers
+// they equal glibc's results bit for bit.
+static __device__ const double kPtLogTable[16][2] = {   // {1 / c, log c} for the 16 subintervals of [0x1.66p-1, 0x1.66p0)
+  {0x1.661ec79f8f3bep+0, -0x1.57bf7808caadep-2}, {0x1.571ed4aaf883dp+0, -0x1.2bef0a7c06ddbp-2}, {0x1.49539f0f010bp+0, -0x1.01eae7f513a67p-2},
+  {0x1.3c995b0b80385p+0, -0x1.b31d8a68224e9p-3}, {0x1.30d190c8864a5p+0, -0x1.6574f0ac07758p-3}, {0x1.25e227b0b8eap+0, -0x1.1aa2bc79c81p-3},
+  {0x1.1bb4a4a1a343fp+0, -0x1.a4e76ce8c0e5ep-4}, {0x1.12358f08ae5bap+0, -0x1.1973c5a611cccp-4}, {0x1.0953f419900a7p+0, -0x1.252f438e10c1ep-5},
+  {0x1p+0, 0x0p+0}, {0x1.e608cfd9a47acp-1, 0x1.aa5aa5df25984p-5}, {0x1.ca4b31f026aap-1, 0x1.c5e53aa362eb4p-4},
+  {0x1.b2036576afce6p-1, 0x1.526e57720db08p-3}, {0x1.9c2d163a1aa2dp-1, 0x1.bc2860d22477p-3}, {0x1.886e6037841edp-1, 0x1.1058bc8a07ee1p-2},
+  {0x1.767dcf5534862p-1, 0x1.4043057b6ee09p-2}};
+
+// log x for a normal x in (0, 1]
+__device__ __forceinline__ float pt_logf(float x)
+{
+  const uint32_t ix = __float_as_uint(x);
+  if (ix == 0x3f800000u) return 0.0f;
+  const uint32_t tmp = ix - 0x3f330000u;              // x = 2^k z with z in [0x1.66p-1, 0x1.66p0), i the subinterval of z
+  const uint32_t i = (tmp >> 19) & 15u;
+  const int k = (int)tmp >> 23;
+  const double z = (double)__uint_as_float(ix - (tmp & 0xff800000u));
+  const double r = z * kPtLogTable[i][0] - 1.0;       // log x = log1p(r) + log c + k ln 2
+  const double y0 = kPtLogTable[i][1] + (double)k * 0x1.62e42fefa39efp-1;
+  const double r2 = r * r;
+  double y = 0x1.5575b0be00b6ap-2 * r + -0x1.ffffef20a4123p-2;
+  y = -0x1.00ea348b88334p-2 * r2 + y;
+  return (float)(y * r2 + (y0 + r));
+}
+
+// sin y and cos y for y in [0, 120)
+__device__ __forceinline__ void pt_sincosf(float y, float* sinp, float* cosp)
+{
+  double x = (double)y;
+  int n = 0;
+  double sign = 1.0, cs = 1.0;
+  if (y >= 0x1.8p-1f) {   // (glibc compares the top 12 bits with pi / 4's: from 0.75 on) x = n pi / 2 + remainder in [-pi / 4, pi / 4]
+    n = ((int)(x * 0x1.45F306DC9C883p+23) + 0x800000) >> 24;
+    x = x - (double)n * 0x1.921FB54442D18p0;
+    sign = ((n + 1) & 2) ? -1.0 : 1.0;     // the sine's sign in quadrants 0 .. 3: + - - +
+    cs = (n & 2) ? -1.0 : 1.0;             // the cosine polynomial's
+  } else if (y < 0x1p-12f) {
+    *sinp = y; *cosp = 1.0f;
+    return;
+  }
+  const double x2 = x * x;
+  x = x * sign;
+  const double x3 = x2 * x, x4 = x2 * x2;
+  const double c2 = cs * -0x1.6c087e89a359dp-10 + x2 * (cs * 0x1.99343027bf8c3p-16);
+  const double s1 = 0x1.1107605230bc4p-7 + x2 * -0x1.994eb3774cf24p-13;
+  const double c1 = cs * 0x1p0 + x2 * (cs * -0x1.ffffffd0c621cp-2);
+  const double x5 = x3 * x2, x6 = x4 * x2;
+  const double s = x + x3 * -0x1.555545995a603p-3;
+  const double c = c1 + x4 * (cs * 0x1.55553e1068f19p-5);
+  const float sv = (float)(s + x5 * s1), cv = (float)(c + x6 * c2);
+  *sinp = (n & 1) ? cv : sv;              // odd quadrants swap the two
+  *cosp = (n & 1) ? sv : cv;
+}
+
 // DeltaTrackingIter::hashit (:545-573)
 __device__ __forceinline__ bool pt_hashit(const RenderParams& p, PtRay& r, float& rayt)
 {
   const vec3f m_dir = r.dir * p.mc_rcp;
   bool found_hit = false;
-  float tau = -logf(1.0f - r.next_float());
+  float tau = -pt_logf(1.0f - r.next_float());
   float t = r.it.next_cell_begin + r.tnear;
   while (dda_next(r.it, m_dir, r.tnear, r.tfar, p.mc_dims, [&](vec3i c, float /*t0*/, float t1) -> bool {
     r.majorant = opacity_upper_bound(p, c) * p.density_scale;
@@ -98,7 +162,7 @@ __device__ __forceinline__ vec3f pt_uniform_sample_sphere(float sx, float sy)
   const float cos_theta = 1.0f - 2.0f * sy;
   const float sin_theta = 2.0f * sqrtf(sy * (1.0f - sy));
   float sp, cp;
-  sincosf(phi, &sp, &cp);
+  pt_sincosf(phi, &sp, &cp);
   return {cp * sin_theta, sp * sin_theta, cos_theta};
 }
 

@@ -13,12 +13,16 @@ the FUNCTION: an output on its L1 target (the gradient is a sign), or a ReLU uni
 the order of the sum).  Targets and training coordinates are therefore drawn away from both (away_from_relu_kinks).  The 2^-8 bar holds the
 independent oracle end to end; the inference kernel itself is held layer by layer, at rounding level, by tests/test_gpu_inference_stages.py."""
 import os
+import sys
 
 import numpy as np
 import pytest
 
 from instantvnr_amd import api
 from instantvnr_amd import synthetic as syn
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import neural_pt_cases as npc  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -439,13 +443,16 @@ def test_randomly_drawn_models_render_alike_through_the_in_shader_and_the_stream
     marching loop; the streaming path: march / evaluate / compose per iteration).  On random models of every width (16 / 32 / 64 / 128) and
     kind (round 5: the in-shader kernels are instantiated for all of them; shapes outside their list take the streaming path either way)
     the network values are the same bits, so ray marching differs only by the streaming path's resume rounding (PSNR > 70 dB) and path
-    tracing not at all."""
+    tracing not at all.  Two black frames are equal whatever the path tracer does after a real collision, so the draws of modes 14 / 15 scale
+    their MLP weights by width as the lit models of tests/neural_pt_cases.py do (on the host, with the oracle alone, 4 of the 4 such draws of
+    the default seed are lit that way and 2 of 4 without), the lit share of each goes into the log, and a third of them must be lit."""
     from instantvnr_amd._lib import check, lib
     n = int(os.environ.get("VNR_FUZZ_IN_SHADER", "16"))
     rng = np.random.default_rng(int(os.environ.get("VNR_FUZZ_SEED", "20260410")) + 31)
     colors, alphas = syn.tfn_ramp_with_bumps()
-    failures = []
+    failures, pt_draws, lit_draws = [], 0, 0
     for i in range(n):
+        lit = None
         F = int(rng.choice([1, 2, 4, 8]))
         L = int(rng.integers(2, min(MAX_LEVELS[F], 12) + 1))
         base = int(rng.integers(2, 9))
@@ -473,7 +480,7 @@ def test_randomly_drawn_models_render_alike_through_the_in_shader_and_the_stream
             nv = api.vnrCreateNeuralVolume(cfg, sv, online_macrocell_construction=False)
             info = api.neural_info(nv)
             api.neural_set_params_fp16(nv, syn.random_params(info["n_params"], oracle.mlp_n_params(info["padded_width"], W, H - 1), seed=100 + i,
-                                                             mlp_scale=(0.5 if W == 128 else 1.0) * (0.7 if H > 3 else 1.0)))
+                                                             mlp_scale=(npc.MLP_SCALE_BY_WIDTH[W] if mode in (14, 15) else 0.5 if W == 128 else 1.0) * (0.7 if H > 3 else 1.0)))
             tfn = api.vnrCreateTransferFunction()
             api.vnrTransferFunctionSetColor(tfn, colors); api.vnrTransferFunctionSetAlpha(tfn, alphas); api.vnrTransferFunctionSetValueRange(tfn, (0, 1))
             v = rng.normal(size=3); v /= np.linalg.norm(v)
@@ -495,6 +502,10 @@ def test_randomly_drawn_models_render_alike_through_the_in_shader_and_the_stream
                     acc.append(api.vnrRendererMapFrame(r).copy())
                 frames[kernel], hits[kernel] = acc, api.vnrRendererGetFrameStats(r)["n_rays_hit"]
             assert hits[1] == hits[0], ("rays hit", hits)
+            if mode in (14, 15):
+                lit = npc.lit_share(frames[1][0])
+                pt_draws += 1
+                lit_draws += lit >= 0.03          # the floor of the dense-volume path-tracing tests (tests/test_gpu_render.py)
             for k in range(2):
                 a, b = frames[1][k], frames[0][k]
                 assert np.isfinite(a).all() and np.isfinite(b).all()
@@ -507,8 +518,9 @@ def test_randomly_drawn_models_render_alike_through_the_in_shader_and_the_stream
             failures.append((d, repr(e)[:300]))
         if os.environ.get("VNR_FUZZ_LOG"):
             with open(os.environ["VNR_FUZZ_LOG"], "a") as f:
-                f.write(f"in-shader {d} {'FAIL ' + failures[-1][1] if failures and failures[-1][0] is d else 'ok'}\n")
+                f.write(f"in-shader {d} {'' if lit is None else f'lit {lit:.3f} '}{'FAIL ' + failures[-1][1] if failures and failures[-1][0] is d else 'ok'}\n")
     assert not failures, failures
+    assert 3 * lit_draws >= pt_draws, ("path-tracing draws that are lit", lit_draws, pt_draws)
 
 
 # ------------------------------------------------------------------------------------------------ dense volumes: sampling, macrocells, DDA, camera

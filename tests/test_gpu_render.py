@@ -1,10 +1,16 @@
 """GPU parity of the march path (through the C-ABI): ground-truth sampling, macrocells, the sample-streaming
 renderer (mode 5) on a dense volume and on a neural volume, the monolithic marcher (mode 4), and tiles."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
 from instantvnr_amd import api
 from instantvnr_amd import synthetic as syn
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import neural_pt_cases as npc  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -612,7 +618,8 @@ def test_path_tracing_streaming_matches_oracle(oracle, scene):
     """VNR_PATHTRACING_SAMPLE_STREAMING (mode 14) on a dense volume against the oracle's restatement of
     method_pathtracing.cu:532-813, two accumulated frames.  A path is a chain of decisions on random numbers (collision or not,
     Russian roulette), so a last-bit difference in logf / sincosf between the device and glibc can send a pixel down another
-    path: the bar is on how many pixels agree, and the rest must still be plausible radiance."""
+    path: the bar is on how many pixels agree, and the rest must still be plausible radiance.  (Since csrc/pt_device.h restates glibc's logf and
+    sincosf the two do agree; the bar stays where it was.)"""
     r = make_renderer(scene, scene["sv"], mode=14)
     api.vnrRendererSetVolumeDensityScale(r, 6.0)
     mo = api.volume_macrocell(scene["sv"])["max_opacity"]
@@ -873,33 +880,18 @@ def test_in_shader_kernel_falls_back_where_it_has_no_instance(oracle, scene):
         assert np.array_equal(api.vnrRendererMapFrame(r6), api.vnrRendererMapFrame(r5))
 
 
-# every FullyFusedMLP width the reference's in-shader dispatch instantiates (16 / 32 / 64, method_raymarching.cu:1192-1244; 128, refused
-# there at :1210, comes with the template here) and models of the GENERAL kind (grid_device.h), F = 1 .. 8
-IN_SHADER_MODELS = {
-    "w16": dict(W=16, L=16, F=2, H=3),
-    "w32": dict(W=32, L=16, F=2, H=3),
-    "w128": dict(W=128, L=8, F=4, H=2, scale=0.5),
-    "w16-f1": dict(W=16, L=16, F=1, H=2),
-    "w32-f8": dict(W=32, L=8, F=8, H=2),
-    "w64-sigmoid-exp": dict(W=64, L=8, F=2, H=2, act="Sigmoid", out_act="Exponential", scale=0.5),
-    "w32-nearest-quantized": dict(W=32, L=16, F=2, H=2, interp="Nearest", qt=0.05),
-    "w16-tiled-smoothstep": dict(W=16, L=8, F=4, H=3, gtype="Tiled", interp="Smoothstep", act="Squareplus"),
-}
+# every FullyFusedMLP width the reference's in-shader dispatch instantiates and models of the GENERAL kind: tests/neural_pt_cases.py
+IN_SHADER_MODELS = npc.IN_SHADER_MODELS
+MARCHING_MLP_SCALE = {"w128": 0.5, "w64-sigmoid-exp": 0.5}   # (the ray-marching modes keep the parameters they have always been run on)
 
 
-def _in_shader_model(oracle, scene, name, seed):
-    m = IN_SHADER_MODELS[name]
-    cfg = syn.model_config(n_levels=m["L"], n_features=m["F"], log2_hashmap_size=14, base_resolution=4, n_hidden_layers=m["H"], per_level_scale=1.4,
-                           n_neurons=m["W"])
-    cfg["network"]["activation"] = m.get("act", "ReLU")
-    cfg["network"]["output_activation"] = m.get("out_act", "None")
-    cfg["encoding"]["interpolation"] = m.get("interp", "Linear")
-    if "gtype" in m: cfg["encoding"]["type"] = m["gtype"]
-    if "qt" in m: cfg["encoding"]["quantize_threshold"] = m["qt"]
-    nv = api.vnrCreateNeuralVolume(cfg, scene["sv"], online_macrocell_construction=False)
-    info = api.neural_info(nv)
-    api.neural_set_params_fp16(nv, syn.random_params(info["n_params"], oracle.mlp_n_params(info["padded_width"], m["W"], m["H"] - 1), seed=seed,
-                                                     mlp_scale=m.get("scale", 1.0)))
+def _in_shader_model(oracle, scene, name, seed=None, mlp_scale=None):
+    """a model of the case table; its own seed and weight scale (searched for a lit path-traced frame) unless others are given"""
+    case = npc.CASES[name]
+    nv = api.vnrCreateNeuralVolume(npc.model_config(case), scene["sv"], online_macrocell_construction=False)
+    params = npc.parameters(oracle, case, seed, mlp_scale)
+    assert api.neural_info(nv)["n_params"] == params.size
+    api.neural_set_params_fp16(nv, params)
     return nv
 
 
@@ -907,11 +899,15 @@ def _in_shader_model(oracle, scene, name, seed):
 def test_in_shader_kernels_of_every_width_and_kind(oracle, scene, name):
     """modes 6 / 9 / 12 / 14 / 15 on models of 16, 32 and 128 neurons and of the GENERAL kind take the in-shader kernel (ONE launch per frame:
     n_iterations == 1) and give the streaming path's frame: bit for bit in the path-tracing modes (the same chain of decisions on the same
-    network bits), to the streaming path's resume rounding in the marching modes (the bars of the 64-neuron test above); hit rays equal"""
-    nv = _in_shader_model(oracle, scene, name, seed=77)
+    network bits), to the streaming path's resume rounding in the marching modes (the bars of the 64-neuron test above); hit rays equal.
+    The path-tracing modes run on the case table's parameters, on which the frame is lit (tests/test_neural_pt_cases_host.py): two black
+    frames are equal whatever the scatter and shadow code does"""
+    marching = _in_shader_model(oracle, scene, name, seed=77, mlp_scale=MARCHING_MLP_SCALE.get(name, 1.0))
+    lit = _in_shader_model(oracle, scene, name)
     size = (64, 48)
     for mode in (6, 9, 12, 14, 15):
         frames, stats = {}, {}
+        nv = lit if mode >= 14 else marching
         for kernel in (1, 0):
             r = make_renderer(scene, nv, size=size, mode=mode)
             if mode >= 14: api.vnrRendererSetVolumeDensityScale(r, 0.5)
@@ -925,6 +921,7 @@ def test_in_shader_kernels_of_every_width_and_kind(oracle, scene, name):
         if mode >= 14:
             assert stats[1]["n_samples"] == stats[0]["n_samples"]
             assert np.array_equal(frames[1], frames[0]), (name, mode)
+            assert npc.lit_share(frames[1]) >= npc.MIN_LIT, (name, mode, npc.lit_share(frames[1]))
         else:
             d = np.abs(frames[1] - frames[0])
             assert d.max() < 2e-3 and psnr(frames[1], frames[0]) > 70, (name, mode, d.max(), psnr(frames[1], frames[0]))
@@ -935,7 +932,7 @@ def test_in_shader_path_tracing_kernel_equals_the_streaming_path_tracer(oracle, 
     """modes 14 / 15 on a neural volume through in_shader_pt_kernel (the default for path tracing: it is the faster of the two) (one launch, the network inside the delta-tracking loop): per pixel the
     same chain of decisions on the same random numbers with the same network bits as the streaming path tracer, so the frames are
     equal BIT FOR BIT over accumulated frames, hit rays and evaluations equal"""
-    nv, _, _, _ = _neural_c4_shape(oracle, scene, seed=41)
+    nv = _in_shader_model(oracle, scene, "c4")      # the C4 shape on the case table's parameters: a lit frame
     size = (96, 80)
     frames, stats = {}, {}
     for kernel in (1, 0):
@@ -953,6 +950,7 @@ def test_in_shader_path_tracing_kernel_equals_the_streaming_path_tracer(oracle, 
     for k in range(3):
         assert np.array_equal(frames[1][k], frames[0][k])
     assert frames[1][2][..., 3].min() == 1.0 and frames[1][2][..., :3].max() > 0.1
+    assert npc.lit_share(frames[1][0]) >= npc.MIN_LIT, npc.lit_share(frames[1][0])      # scatter, shadow rays and accumulation did run
 
 
 def test_parameters_that_would_never_finish_a_frame_are_refused_by_name(scene):

@@ -9,6 +9,7 @@
 #include <memory>
 
 #include "correction_budget.h"
+#include "correction_record.h"
 #include "dist.h"
 #include "renderer.h"
 #include "scene.h"
@@ -86,6 +87,70 @@ void* dup_bytes(const void* p, size_t n)
   if (!out) throw std::runtime_error("out of host memory");
   if (n) std::memcpy(out, p, n);
   return out;
+}
+
+// vnrAmdCorrectionSerialize*, to the host and into device memory; a device is asked for only where the route runs on one
+int serialize_correction(vnrAmdCorrection c, CorrectionForm form, void** bytes, size_t* size)
+{
+  return guarded([&]() {
+    Correction* k = as_correction(c);
+    if (!bytes || !size) throw std::runtime_error("null result");
+    if (correction_needs_device(*k, form, false) && !Runtime::get().ready()) Runtime::get().init(-1);
+    const std::vector<uint8_t> b = correction_serialize(*k, form, Runtime::get().stream);
+    *bytes = dup_bytes(b.data(), b.size());
+    *size = b.size();
+  });
+}
+int serialize_correction_to_device(vnrAmdCorrection c, CorrectionForm form, void* d_bytes, size_t capacity, size_t* size, void* stream)
+{
+  return guarded([&]() {
+    Correction* k = as_correction(c);
+    if (!size) throw std::runtime_error("null result");
+    if (correction_needs_device(*k, form, d_bytes != nullptr) && !Runtime::get().ready()) Runtime::get().init(-1);
+    correction_serialize_to_device(*k, form, d_bytes, capacity, size, (hipStream_t)stream);
+  });
+}
+// the tail of vnrAmdCreateCorrectionFrom*Bytes: what only a build knows is unknown (worst_after = -1, -1, -1 and the counts 0 likewise)
+vnrAmdCorrection_t* read_correction(std::shared_ptr<Correction> k, CorrectionHeader h, std::vector<CorrectionCellEntry> cells)
+{
+  k->data.h = h;
+  k->data.cells = std::move(cells);
+  k->max_abs_before = std::numeric_limits<double>::quiet_NaN();
+  return new vnrAmdCorrection_t{std::move(k)};
+}
+// vnrAmdNeuralVolumeBuildCorrectionWithinBytes / CodedWithinBytes after their own refusals: the search over rate passes, the build at its tolerance,
+// and what was promised is what was built.  FIXED, PACKED: the two-call build (the device pack stays cached); CODED: the direct build, encoded once.
+vnrAmdCorrection_t* build_within_bytes(vnrAmdVolume v, const DeviceSource& ref, float range_lo, float range_hi, uint64_t max_bytes, CorrectionForm form,
+                                       double eps_hi, int rounds, vnrAmdCorrectionBudget* report)
+{
+  correction_budget_check(eps_hi, rounds);
+  NeuralVolume* n = as_neural(v);
+  const bool coded = form == CorrectionForm::Coded, packed = form == CorrectionForm::Packed;
+  const CorrectionBudgetResult r = correction_budget_search(
+      [&](const double* eps, int n_eps, uint64_t* bytes, int* refused) {
+        CorrectionRateCoded rates[kCorrectionBudgetLadder];
+        CorrectionRate plain[kCorrectionBudgetLadder];
+        if (coded) n->correction_rates_coded(ref, range_lo, range_hi, eps, n_eps, rates);
+        else n->correction_rates(ref, range_lo, range_hi, eps, n_eps, plain);
+        for (int k = 0; k < n_eps; ++k) {
+          const CorrectionRate& rate = coded ? rates[k].rate : plain[k];
+          bytes[k] = coded ? rates[k].coded_serialized_bytes : (packed ? rate.packed_serialized_bytes : rate.serialized_bytes);
+          refused[k] = rate.refused;
+        }
+      },
+      max_bytes, eps_hi, rounds);
+  std::shared_ptr<Correction> corr = coded ? n->build_correction_packed(ref, range_lo, range_hi, r.eps) : n->build_correction(ref, range_lo, range_hi, r.eps);
+  hipStream_t s = Runtime::get().stream;
+  const uint64_t built = kCorrectionHeaderBytes + 8 * corr->data.cells.size() +
+                         (coded ? correction_coded_payload(*corr, s) : (packed ? correction_packed_payload(*corr, s) : correction_fixed_payload(*corr, s))).size();
+  if (built != r.bytes) {
+    char e[40];
+    std::snprintf(e, sizeof(e), "%.17g", r.eps);
+    throw std::runtime_error(std::string("internal error: the correction built at eps ") + e + " has " + std::to_string(built) + " serialised bytes" +
+                             (coded ? " in the coded form" : "") + ", the rate pass gave " + std::to_string(r.bytes));
+  }
+  *report = vnrAmdCorrectionBudget{r.eps, r.bytes, r.eps_tighter, r.bytes_tighter, r.rate_passes};
+  return new vnrAmdCorrection_t{std::move(corr)};
 }
 }  // namespace
 
@@ -612,13 +677,7 @@ vnrAmdCorrection vnrAmdNeuralVolumeBuildCorrectionPacked(vnrAmdVolume v, const v
 }
 int vnrAmdCorrectionSerializePackedToDevice(vnrAmdCorrection c, void* d_bytes, size_t capacity, size_t* size, void* stream)
 {
-  return guarded([&]() {
-    Correction* k = as_correction(c);
-    if (!size) throw std::runtime_error("null result");
-    if (!k->planes_uploaded) k->transcode_coded_on_host();   // (read from coded bytes and never used on the device: no device is asked for)
-    if (!Runtime::get().ready() && (d_bytes || (!k->data.cells.empty() && !k->has_packed))) Runtime::get().init(-1);
-    correction_serialize_packed_to_device(*k, d_bytes, capacity, size, (hipStream_t)stream);
-  });
+  return serialize_correction_to_device(c, CorrectionForm::Packed, d_bytes, capacity, size, stream);
 }
 int vnrAmdNeuralVolumeCorrectionRates(vnrAmdVolume v, const void* d_ref, int value_type, const int64_t strides[3], float range_lo, float range_hi,
                                       const double* eps, int n_eps, void* stream, vnrAmdCorrectionRate* out)
@@ -638,32 +697,7 @@ vnrAmdCorrection vnrAmdNeuralVolumeBuildCorrectionWithinBytes(vnrAmdVolume v, co
     if (!report) throw std::runtime_error("null result");
     if (form != VNR_AMD_CORRECTION_FORM_FIXED && form != VNR_AMD_CORRECTION_FORM_PACKED)
       throw std::runtime_error("unknown serialised form " + std::to_string(form) + " (0: fixed-width, 1: packed)");
-    correction_budget_check(eps_hi, rounds);
-    NeuralVolume* n = as_neural(v);
-    const DeviceSource ref{d_ref, value_type, strides, (hipStream_t)stream};
-    const bool packed = form == VNR_AMD_CORRECTION_FORM_PACKED;
-    const CorrectionBudgetResult r = correction_budget_search(
-        [&](const double* eps, int n_eps, uint64_t* bytes, int* refused) {
-          CorrectionRate rates[kCorrectionBudgetLadder];
-          n->correction_rates(ref, range_lo, range_hi, eps, n_eps, rates);
-          for (int k = 0; k < n_eps; ++k) {
-            bytes[k] = packed ? rates[k].packed_serialized_bytes : rates[k].serialized_bytes;
-            refused[k] = rates[k].refused;
-          }
-        },
-        max_bytes, eps_hi, rounds);
-    std::shared_ptr<Correction> corr = n->build_correction(ref, range_lo, range_hi, r.eps);
-    // what was promised is what was built (PACKED: the device pack, which stays cached for SerializePacked)
-    const uint64_t built = packed ? kCorrectionHeaderBytes + 8 * corr->data.cells.size() + correction_packed_payload(*corr, Runtime::get().stream).size()
-                                  : correction_serialized_bytes(corr->data);
-    if (built != r.bytes) {
-      char e[40];
-      std::snprintf(e, sizeof(e), "%.17g", r.eps);
-      throw std::runtime_error(std::string("internal error: the correction built at eps ") + e + " has " + std::to_string(built) +
-                               " serialised bytes, the rate pass gave " + std::to_string(r.bytes));
-    }
-    *report = vnrAmdCorrectionBudget{r.eps, r.bytes, r.eps_tighter, r.bytes_tighter, r.rate_passes};
-    return new vnrAmdCorrection_t{std::move(corr)};
+    return build_within_bytes(v, DeviceSource{d_ref, value_type, strides, (hipStream_t)stream}, range_lo, range_hi, max_bytes, (CorrectionForm)form, eps_hi, rounds, report);
   });
 }
 int vnrAmdNeuralVolumeCorrectionRatesCoded(vnrAmdVolume v, const void* d_ref, int value_type, const int64_t strides[3], float range_lo, float range_hi,
@@ -684,30 +718,7 @@ vnrAmdCorrection vnrAmdNeuralVolumeBuildCorrectionCodedWithinBytes(vnrAmdVolume 
 {
   return guarded_new<vnrAmdCorrection_t>([&]() {
     if (!report) throw std::runtime_error("null result");
-    correction_budget_check(eps_hi, rounds);
-    NeuralVolume* n = as_neural(v);
-    const DeviceSource ref{d_ref, value_type, strides, (hipStream_t)stream};
-    const CorrectionBudgetResult r = correction_budget_search(
-        [&](const double* eps, int n_eps, uint64_t* bytes, int* refused) {
-          CorrectionRateCoded rates[kCorrectionBudgetLadder];
-          n->correction_rates_coded(ref, range_lo, range_hi, eps, n_eps, rates);
-          for (int k = 0; k < n_eps; ++k) {
-            bytes[k] = rates[k].coded_serialized_bytes;
-            refused[k] = rates[k].rate.refused;
-          }
-        },
-        max_bytes, eps_hi, rounds);
-    // the direct build: the planes and their index, no fixed-width payload; then the device encode, once, cached for SerializeCoded
-    std::shared_ptr<Correction> corr = n->build_correction_packed(ref, range_lo, range_hi, r.eps);
-    const uint64_t built = kCorrectionHeaderBytes + 8 * corr->data.cells.size() + correction_coded_payload(*corr, Runtime::get().stream).size();
-    if (built != r.bytes) {
-      char e[40];
-      std::snprintf(e, sizeof(e), "%.17g", r.eps);
-      throw std::runtime_error(std::string("internal error: the correction built at eps ") + e + " has " + std::to_string(built) +
-                               " serialised bytes in the coded form, the rate pass gave " + std::to_string(r.bytes));
-    }
-    *report = vnrAmdCorrectionBudget{r.eps, r.bytes, r.eps_tighter, r.bytes_tighter, r.rate_passes};
-    return new vnrAmdCorrection_t{std::move(corr)};
+    return build_within_bytes(v, DeviceSource{d_ref, value_type, strides, (hipStream_t)stream}, range_lo, range_hi, max_bytes, CorrectionForm::Coded, eps_hi, rounds, report);
   });
 }
 int vnrAmdCorrectionGetInfo(vnrAmdCorrection c, vnrAmdCorrectionInfo* out)
@@ -715,10 +726,9 @@ int vnrAmdCorrectionGetInfo(vnrAmdCorrection c, vnrAmdCorrectionInfo* out)
   return guarded([&]() {
     Correction* k = as_correction(c);
     if (!out) throw std::runtime_error("null result");
-    if (!k->direct) k->host_payload();   // (a correction read from packed bytes: its fixed-width sizes)
     const CorrectionHeader& h = k->data.h;
-    // a direct build moves nothing for this: the fixed-width payload's size follows from the entries
-    const uint64_t payload_bytes = k->direct ? correction_fixed_payload_bytes(h, k->data.cells) : k->data.payload.size();
+    // nothing is moved or converted for this: the fixed-width payload's size follows from the entries
+    const uint64_t payload_bytes = correction_fixed_payload_bytes(h, k->data.cells);
     *out = vnrAmdCorrectionInfo{};
     for (int a = 0; a < 3; ++a) { out->dims[a] = h.dims[a]; out->worst_after[a] = k->worst_after[a]; }
     out->value_type = h.value_type; out->kind = (int)h.kind; out->eps = h.eps; out->range_lo = h.range_lo; out->range_hi = h.range_hi;
@@ -729,95 +739,51 @@ int vnrAmdCorrectionGetInfo(vnrAmdCorrection c, vnrAmdCorrectionInfo* out)
 }
 int vnrAmdCorrectionSerialize(vnrAmdCorrection c, void** bytes, size_t* size)
 {
-  return guarded([&]() {
-    Correction* k = as_correction(c);
-    if (!bytes || !size) throw std::runtime_error("null result");
-    if (k->direct && !k->has_packed) correction_packed_payload(*k, Runtime::get().stream);   // a direct build: table and planes, downloaded once
-    k->host_payload();
-    const std::vector<uint8_t> b = correction_write(k->data);
-    *bytes = dup_bytes(b.data(), b.size());
-    *size = b.size();
-  });
+  return serialize_correction(c, CorrectionForm::Fixed, bytes, size);
 }
 vnrAmdCorrection vnrAmdCreateCorrectionFromBytes(const void* bytes, size_t size)
 {
   return guarded_new<vnrAmdCorrection_t>([&]() {
-    auto k = std::make_shared<Correction>();
-    k->data = correction_parse(bytes, size);
-    k->max_abs_before = std::numeric_limits<double>::quiet_NaN();   // known to the build alone; worst_after = -1, -1, -1 and the counts 0 likewise
-    return new vnrAmdCorrection_t{std::move(k)};
+    auto k = std::make_shared<Correction>(CorrectionOrigin::FixedBytes);
+    CorrectionData p = correction_parse(bytes, size);
+    k->data.payload = std::move(p.payload);
+    return read_correction(std::move(k), p.h, std::move(p.cells));
   });
 }
 int vnrAmdCorrectionSerializePacked(vnrAmdCorrection c, void** bytes, size_t* size)
 {
-  return guarded([&]() {
-    Correction* k = as_correction(c);
-    if (!bytes || !size) throw std::runtime_error("null result");
-    if (!k->planes_uploaded) k->transcode_coded_on_host();   // (read from coded bytes and never used on the device: no device is asked for)
-    if (!k->has_packed) {   // the device pack, once
-      if (!k->data.cells.empty() && !Runtime::get().ready()) Runtime::get().init(-1);
-      correction_packed_payload(*k, Runtime::get().stream);
-    }
-    const std::vector<uint8_t> b = correction_packed_write(k->data.h, k->data.cells, k->packed_payload);
-    *bytes = dup_bytes(b.data(), b.size());
-    *size = b.size();
-  });
+  return serialize_correction(c, CorrectionForm::Packed, bytes, size);
 }
 vnrAmdCorrection vnrAmdCreateCorrectionFromPackedBytes(const void* bytes, size_t size)
 {
   return guarded_new<vnrAmdCorrection_t>([&]() {
-    auto k = std::make_shared<Correction>();
+    auto k = std::make_shared<Correction>(CorrectionOrigin::PackedBytes);
     CorrectionPacked p = correction_packed_parse(bytes, size);
-    k->data.h = p.h;
-    k->data.cells = std::move(p.cells);
     k->packed_payload = std::move(p.payload);
-    k->has_packed = k->from_packed = true;
-    k->max_abs_before = std::numeric_limits<double>::quiet_NaN();   // as CreateCorrectionFromBytes
-    return new vnrAmdCorrection_t{std::move(k)};
+    return read_correction(std::move(k), p.h, std::move(p.cells));
   });
 }
 int vnrAmdCorrectionSerializeCoded(vnrAmdCorrection c, void** bytes, size_t* size)
 {
-  return guarded([&]() {
-    Correction* k = as_correction(c);
-    if (!bytes || !size) throw std::runtime_error("null result");
-    // (a correction that holds codes or planes on the device has initialised the runtime; any other is transcoded on the host)
-    const std::vector<uint8_t> b = correction_coded_write(k->data.h, k->data.cells, correction_coded_payload(*k, Runtime::get().stream));
-    *bytes = dup_bytes(b.data(), b.size());
-    *size = b.size();
-  });
+  return serialize_correction(c, CorrectionForm::Coded, bytes, size);
 }
 vnrAmdCorrection vnrAmdCreateCorrectionFromCodedBytes(const void* bytes, size_t size)
 {
   return guarded_new<vnrAmdCorrection_t>([&]() {
-    auto k = std::make_shared<Correction>();
+    auto k = std::make_shared<Correction>(CorrectionOrigin::CodedBytes);
     CorrectionCoded p = correction_coded_parse(bytes, size);
-    k->data.h = p.h;
-    k->data.cells = std::move(p.cells);
     k->coded_payload = std::move(p.payload);
     k->group_table = std::move(p.group_nbits);
-    k->has_coded = k->from_coded = true;
-    if (k->data.cells.empty()) k->has_packed = k->from_packed = true;   // no group, no plane: the packed payload is empty, too
-    k->max_abs_before = std::numeric_limits<double>::quiet_NaN();   // as CreateCorrectionFromBytes
-    return new vnrAmdCorrection_t{std::move(k)};
+    return read_correction(std::move(k), p.h, std::move(p.cells));
   });
 }
 int vnrAmdCorrectionSerializeCodedToDevice(vnrAmdCorrection c, void* d_bytes, size_t capacity, size_t* size, void* stream)
 {
-  return guarded([&]() {
-    Correction* k = as_correction(c);
-    if (!size) throw std::runtime_error("null result");
-    if (!Runtime::get().ready() && d_bytes) Runtime::get().init(-1);   // (the size alone of a correction that lives on the host asks for no device)
-    correction_serialize_coded_to_device(*k, d_bytes, capacity, size, (hipStream_t)stream);
-  });
+  return serialize_correction_to_device(c, CorrectionForm::Coded, d_bytes, capacity, size, stream);
 }
 int vnrAmdNeuralVolumeDecodeToDeviceCorrected(vnrAmdVolume v, vnrAmdCorrection c, void* d_out, const int64_t strides[3], void* stream, int verify_params)
 {
-  return guarded([&]() {
-    NeuralVolume* n = as_neural(v);
-    Correction* k = as_correction(c);
-    n->decode_to_device_corrected(*k, DeviceTarget{d_out, k->data.h.value_type, strides, (hipStream_t)stream}, nullptr, nullptr, verify_params != 0);
-  });
+  return vnrAmdNeuralVolumeDecodeBoxToDeviceCorrected(v, c, d_out, strides, nullptr, nullptr, stream, verify_params);   // the whole grid
 }
 int vnrAmdNeuralVolumeDecodeBoxToDeviceCorrected(vnrAmdVolume v, vnrAmdCorrection c, void* d_out, const int64_t strides[3], const int box_lo[3],
                                                  const int box_size[3], void* stream, int verify_params)

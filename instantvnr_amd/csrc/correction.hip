@@ -18,9 +18,10 @@
 // build_correction_packed ("corrections built straight into bit planes", at the end of this file) gives build_correction's correction
 // in the packed resident form without the fixed-width codes in between: the rate pass's walk for one tolerance with the error reports
 // taken from it, n_cells pairs through the host (correction_direct.cpp), an index kernel, and the planes of the groups that store any
-// from a second evaluation of those groups alone.  correction_serialize_packed_to_device writes the packed bytes into device memory.
+// from a second evaluation of those groups alone.  What a correction holds afterwards and every conversion of it: correction_store.hip.
 #include "box_walk.h"
 #include "correction_direct.h"
+#include "correction_record.h"
 
 #include <cstdio>
 #include <cstring>
@@ -668,22 +669,21 @@ CellGrid make_cell_grid(vec3i d)
   return CellGrid{(uint32_t)d.x, (uint32_t)d.y, (uint32_t)d.z, (uint32_t)((d.x + 15) / 16), (uint32_t)((d.y + 15) / 16)};
 }
 
-// per-cell {offset, width} of all n_cells cells from the flagged ones, in payload order
-std::vector<CorrectionTableEntry> make_table(const CorrectionData& d, uint64_t n_cells)
-{
-  std::vector<CorrectionTableEntry> t(n_cells, CorrectionTableEntry{~0ull, 0, 0});
-  uint64_t offset = 0;
-  for (const CorrectionCellEntry& e : d.cells) {
-    t[e.cell] = CorrectionTableEntry{offset, e.width, 0};
-    offset += correction_padded_bytes(correction_cell_voxels(d.h.dims, e.cell), e.width);
-  }
-  return t;
-}
-
 void index_to_voxel(uint64_t i, const BoxLayout& L, int out[3])
 {
   const uint64_t yz = i / L.bx;
   out[0] = (int)(i - yz * L.bx); out[1] = (int)(yz % L.by); out[2] = (int)(yz / L.by);
+}
+
+// what a build reports: the counts and the error before, the error after and where it is (a negative maximum: every error is a NaN)
+void set_report(Correction& corr, const Partial& before, const Partial& after, const BoxLayout& L)
+{
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  corr.n_voxels_flagged = before.a;
+  corr.n_nan = before.b;
+  corr.max_abs_before = before.max_abs < 0.0 ? nan : before.max_abs;
+  corr.data.h.max_abs_after = after.max_abs < 0.0 ? nan : after.max_abs;
+  if (!(after.max_abs < 0.0)) index_to_voxel(after.worst, L, corr.worst_after);
 }
 
 }  // namespace
@@ -712,7 +712,7 @@ std::shared_ptr<Correction> NeuralVolume::build_correction(const DeviceSource& r
   const int dims[3] = {grid.x, grid.y, grid.z};
   const uint64_t n_cells = correction_n_cells(dims);
 
-  auto corr = std::make_shared<Correction>();
+  auto corr = std::make_shared<Correction>(CorrectionOrigin::Built);
   CorrectionHeader& h = corr->data.h;
   h.value_type = ref.type;
   for (int a = 0; a < 3; ++a) h.dims[a] = dims[a];
@@ -755,21 +755,17 @@ std::shared_ptr<Correction> NeuralVolume::build_correction(const DeviceSource& r
 
   // the table
   const uint32_t ts = (uint32_t)device_value_type_size(ref.type);
-  uint64_t payload_bytes = 0;
   for (uint64_t cl = 0; cl < n_cells; ++cl) {
     const uint32_t m = cells[cl];
     if (m == 0) continue;
     if (m > 0x7fffffffu) throw std::runtime_error("the tolerance needs codes wider than 32 bits: eps " + std::to_string(eps) + " against a maximum error of " + std::to_string(before.max_abs));
     const uint32_t width = kind == kCorrectionVerbatim ? ts : (m <= 127 ? 1u : (m <= 32767 ? 2u : 4u));
     corr->data.cells.push_back(CorrectionCellEntry{(uint32_t)cl, width});
-    payload_bytes += correction_padded_bytes(correction_cell_voxels(dims, (uint32_t)cl), width);
   }
-  corr->n_voxels_flagged = before.a;
-  corr->n_nan = before.b;
-  corr->max_abs_before = before.max_abs < 0.0 ? std::numeric_limits<double>::quiet_NaN() : before.max_abs;
+  const uint64_t payload_bytes = correction_fixed_payload_bytes(h, corr->data.cells);
   Partial after = before;   // without a flagged cell every voxel stays as decoded
   if (!corr->data.cells.empty()) {
-    const std::vector<CorrectionTableEntry> table = make_table(corr->data, n_cells);
+    const std::vector<CorrectionTableEntry> table = correction_make_table(h, corr->data.cells);
     corr->d_table.upload(table.data(), table.size(), stream);
     corr->d_payload.resize(payload_bytes);
     corr->d_payload.zero(stream);   // (the padding, and what no voxel owns, stays zero)
@@ -793,13 +789,7 @@ std::shared_ptr<Correction> NeuralVolume::build_correction(const DeviceSource& r
     corr->data.payload.resize(payload_bytes);
     corr->d_payload.download(corr->data.payload.data(), payload_bytes, stream);   // (synchronises: `table` and `after` are done with)
   }
-  corr->uploaded = true;
-  if (after.max_abs < 0.0) {   // every voxel's error is a NaN
-    h.max_abs_after = std::numeric_limits<double>::quiet_NaN();
-  } else {
-    h.max_abs_after = after.max_abs;
-    index_to_voxel(after.worst, L, corr->worst_after);
-  }
+  set_report(*corr, before, after, L);
   return corr;
 }
 
@@ -966,64 +956,6 @@ void correction_rates_check(const double* eps, int n_eps, const CorrectionRate* 
       throw std::runtime_error("eps[" + std::to_string(k) + "] must be a finite tolerance >= 0 in data units, got " + str_g(eps[k]));
 }
 
-void correction_make_resident(Correction& corr, hipStream_t stream)
-{
-  const CorrectionData& d = corr.data;
-  if (d.cells.empty()) return;
-  // read from coded bytes and first used here: the streams are decoded on the device (correction_code.hip), the planes are then resident
-  if (corr.coded_pending() && !corr.planes_uploaded && !corr.uploaded && !corr.payload_uploaded) correction_decode_coded_on_device(corr, stream);
-  const uint64_t n_cells = correction_n_cells(d.h.dims);
-  if (corr.resident_form == 0) {
-    if (!corr.uploaded) {
-      const std::vector<CorrectionTableEntry> table = make_table(d, n_cells);
-      corr.d_table.upload(table.data(), table.size(), stream);
-      correction_ensure_device_payload(corr, stream);   // correction_pack.hip: uploaded, or unpacked on the device from the packed payload
-      VNR_HIP_CHECK(hipStreamSynchronize(stream));   // `table` goes out of scope
-      corr.uploaded = true;
-    }
-    if (corr.planes_uploaded) {
-      VNR_HIP_CHECK(hipStreamSynchronize(stream));   // no apply still reads the planes
-      corr.d_packed.release(); corr.d_plane_cells.release(); corr.d_plane_groups.release();
-      corr.planes_uploaded = false;
-    }
-    return;
-  }
-  if (!corr.planes_uploaded) {
-    const std::vector<uint8_t>& packed = correction_packed_payload(corr, stream);   // (the device pack, once, of a correction that has no packed form yet)
-    const CorrectionPlaneIndex ix = correction_plane_index(d.h, d.cells, packed);
-    if (ix.group_word.size() > 0xffffffffull) throw std::runtime_error("the correction has more than 2^32 groups");
-    std::vector<Correction::PlaneCell> cells(n_cells, Correction::PlaneCell{~0ull, 0, 0});
-    for (size_t i = 0; i < d.cells.size(); ++i) cells[d.cells[i].cell] = Correction::PlaneCell{ix.cell_word0[i], (uint32_t)ix.cell_group0[i], 0};
-    std::vector<uint32_t> groups(ix.group_word.size());
-    for (size_t g = 0; g < groups.size(); ++g) groups[g] = (uint32_t)ix.group_word[g] | (uint32_t)packed[g] << 16;
-    corr.d_plane_cells.upload(cells.data(), cells.size(), stream);
-    corr.d_plane_groups.upload(groups.data(), groups.size(), stream);
-    corr.d_packed.upload(packed.data(), packed.size(), stream);   // as it is (hipMalloc aligns it; the planes start at a multiple of 8)
-    VNR_HIP_CHECK(hipStreamSynchronize(stream));   // the host vectors go out of scope
-    corr.planes_uploaded = true;
-  }
-  if (corr.uploaded || corr.payload_uploaded) {
-    VNR_HIP_CHECK(hipStreamSynchronize(stream));   // no apply or pack still reads the fixed-width payload
-    corr.d_payload.release(); corr.d_table.release();
-    corr.uploaded = corr.payload_uploaded = false;
-  }
-}
-
-void correction_set_resident_form(Correction& corr, int form, hipStream_t stream)
-{
-  if (form != 0 && form != 1) throw std::runtime_error("unknown resident form " + std::to_string(form) + " (0: fixed-width, 1: packed)");
-  if (form == corr.resident_form) return;
-  const int before = corr.resident_form;
-  corr.resident_form = form;
-  if (!corr.uploaded && !corr.payload_uploaded && !corr.planes_uploaded) return;   // nothing on the device yet: the first apply brings this form
-  try {
-    correction_make_resident(corr, stream);
-  } catch (...) {
-    corr.resident_form = before;
-    throw;
-  }
-}
-
 void NeuralVolume::decode_to_device_corrected(Correction& corr, const DeviceTarget& out, const int box_lo[3], const int box_size[3], bool verify_params)
 {
   if (!net_.valid()) throw std::runtime_error("neural volume has no valid network");
@@ -1044,7 +976,7 @@ void NeuralVolume::decode_to_device_corrected(Correction& corr, const DeviceTarg
     decode_to_device(DeviceTarget{out.data, h.value_type, out.strides, out.consumer}, box_lo, box_size, nullptr, h.range_lo, h.range_hi);
     return;
   }
-  correction_make_resident(corr, stream);
+  correction_make_resident(corr, corr.resident_form, stream);
   const uint64_t total = L.bx * L.by * L.bz, chunk = std::min(chunk_limit, total);
   const vec3f rdims = {1.0f / (float)grid.x, 1.0f / (float)grid.y, 1.0f / (float)grid.z};
   const uint32_t ox = (uint32_t)lower.x, oy = (uint32_t)lower.y, oz = (uint32_t)lower.z;
@@ -1265,7 +1197,7 @@ std::shared_ptr<Correction> NeuralVolume::build_correction_packed(const DeviceSo
   const uint64_t n_cells = correction_n_cells(dims);
   const uint64_t chunk_groups = std::min(std::max<uint64_t>(1, chunk_samples() / 64), w.n_groups);   // whole groups, as the rate pass
 
-  auto corr = std::make_shared<Correction>();
+  auto corr = std::make_shared<Correction>(CorrectionOrigin::BuiltDirect);
   CorrectionHeader& h = corr->data.h;
   h.value_type = ref.type;
   for (int a = 0; a < 3; ++a) h.dims[a] = dims[a];
@@ -1321,21 +1253,9 @@ std::shared_ptr<Correction> NeuralVolume::build_correction_packed(const DeviceSo
     throw std::runtime_error("the tolerance needs codes wider than 32 bits: eps " + std::to_string(eps) + " against a maximum error of " + std::to_string(before.max_abs));
   if (plan.n_groups > 0xffffffffull) throw std::runtime_error("the correction has more than 2^32 groups");
   corr->data.cells = plan.cells;
-  corr->n_voxels_flagged = before.a;
-  corr->n_nan = before.b;
-  corr->max_abs_before = before.max_abs < 0.0 ? std::numeric_limits<double>::quiet_NaN() : before.max_abs;
-  if (after.max_abs < 0.0) {   // every voxel's error is a NaN
-    h.max_abs_after = std::numeric_limits<double>::quiet_NaN();
-  } else {
-    h.max_abs_after = after.max_abs;
-    index_to_voxel(after.worst, L, corr->worst_after);
-  }
+  set_report(*corr, before, after, L);
   corr->resident_form = 1;
-  corr->direct = true;
-  if (plan.cells.empty()) {   // holds nothing, as every correction without a flagged cell
-    corr->has_packed = true;
-    return corr;
-  }
+  if (plan.cells.empty()) return corr;   // holds nothing, as every correction without a flagged cell
 
   const uint32_t n_flagged = (uint32_t)plan.cells.size();
   const uint64_t table_bytes = correction_group_table_bytes(plan.n_groups);
@@ -1383,36 +1303,7 @@ std::shared_ptr<Correction> NeuralVolume::build_correction_packed(const DeviceSo
     }
     VNR_HIP_CHECK(hipStreamSynchronize(stream));   // the scratch of this call goes out of scope
   }
-  corr->planes_uploaded = true;
   return corr;
-}
-
-void correction_serialize_packed_to_device(Correction& corr, void* d_bytes, size_t capacity, size_t* size, hipStream_t consumer)
-{
-  if (!size) throw std::runtime_error("null result");
-  const CorrectionData& d = corr.data;
-  hipStream_t stream = Runtime::get().stream;
-  uint64_t payload_bytes = 0;   // of the packed payload: the host copy's if there is one, else the resident planes'
-  if (!d.cells.empty()) {
-    if (!corr.has_packed && !corr.planes_uploaded) correction_packed_payload(corr, stream);   // the device pack, cached as by SerializePacked
-    payload_bytes = corr.has_packed ? corr.packed_payload.size() : corr.d_packed.bytes();
-  }
-  std::vector<uint8_t> head = correction_packed_write(d.h, d.cells, std::vector<uint8_t>());
-  std::memcpy(head.data() + 80, &payload_bytes, sizeof(uint64_t));   // payload_bytes of the header (correction_format.h)
-  *size = head.size() + payload_bytes;
-  if (!d_bytes) return;
-  if (capacity < *size)
-    throw std::runtime_error("capacity (" + std::to_string(capacity) + " bytes) is smaller than the packed correction (" + std::to_string(*size) + " bytes)");
-  require_room(d_bytes, *size, "the packed bytes");
-  if (payload_bytes && !corr.planes_uploaded && corr.resident_form == 1) correction_make_resident(corr, stream);   // PACKED: the planes, then device to device
-  EventGuard ev;
-  wait_for(consumer, stream, ev);   // what the destination held may still be being read
-  VNR_HIP_CHECK(hipMemcpyAsync(d_bytes, head.data(), head.size(), hipMemcpyHostToDevice, stream));
-  if (payload_bytes) {
-    if (corr.planes_uploaded) VNR_HIP_CHECK(hipMemcpyAsync((uint8_t*)d_bytes + head.size(), corr.d_packed.ptr, payload_bytes, hipMemcpyDeviceToDevice, stream));
-    else VNR_HIP_CHECK(hipMemcpyAsync((uint8_t*)d_bytes + head.size(), corr.packed_payload.data(), payload_bytes, hipMemcpyHostToDevice, stream));
-  }
-  VNR_HIP_CHECK(hipStreamSynchronize(stream));   // on return the bytes are there; `head` goes out of scope
 }
 
 }  // namespace vnr

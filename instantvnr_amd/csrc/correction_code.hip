@@ -11,15 +11,15 @@
 // Decode: a wave stages its cell's stream in LDS and walks the records in order (all lanes read the same field, a broadcast), each
 // lane collects its own magnitude and sign, and the planes of z leave by ballot exactly as correction_pack.hip writes them, at the
 // places the host parse's group table gives.  Every offset is 64-bit.  tests/correction_coded_ref.py restates the format in numpy.
-#include "box_walk.h"
+// The encoder and the decode launch at the end take what they work on as arguments: when they run is correction_store.hip's.
+#include "correction_wave.h"
+
+#include <cstring>
 
 namespace vnr {
 
 namespace {
 
-constexpr int kWave = 64;
-static_assert(kWave == (int)kCorrectionGroup, "a group is one wavefront");
-constexpr uint32_t kMaxCellBlocks = 1u << 20;   // cells beyond that are reached by block stride
 constexpr uint32_t kStageWords = kCodedMaxCellWords;
 
 // a flagged cell to be encoded
@@ -42,23 +42,6 @@ struct DecodeCell {
   uint64_t stream0, word0;   // its first stream word; its first plane word
   uint32_t stream_words, group0, voxels, width;
 };
-
-__device__ __forceinline__ uint64_t wave_or(uint64_t v)
-{
-  for (int off = kWave / 2; off > 0; off >>= 1) v |= (uint64_t)__shfl_xor((unsigned long long)v, off, kWave);
-  return v;
-}
-
-// exclusive prefix sum over the lanes
-__device__ __forceinline__ uint32_t wave_exclusive_scan(uint32_t v, uint32_t lane)
-{
-  uint32_t incl = v;
-  for (int off = 1; off < kWave; off <<= 1) {
-    const uint32_t t = __shfl_up(incl, off, kWave);
-    if (lane >= (uint32_t)off) incl += t;
-  }
-  return incl - v;
-}
 
 __device__ __forceinline__ uint32_t lanes_below(uint64_t mask, uint32_t lane) { return (uint32_t)__popcll(mask & ((1ull << lane) - 1)); }
 
@@ -235,177 +218,69 @@ __global__ void __launch_bounds__(kWave) correction_code_decode_kernel(const uin
   }
 }
 
-uint32_t cell_blocks(size_t n_cells) { return (uint32_t)std::min<size_t>(n_cells, kMaxCellBlocks); }
-
-bool on_device(const Correction& corr) { return corr.planes_uploaded || corr.uploaded || corr.payload_uploaded; }
-
-// what both encode passes share; lives as long as the kernels run
-struct Encoder {
-  CodeSource src{};
-  bool verbatim = false;
-  uint32_t n = 0;
-  uint64_t words = 0;   // of all streams, after measure()
-  DeviceBuffer<CodeCell> cells{MemTag::Network};
-  DeviceBuffer<uint32_t> group_bits{MemTag::Network}, cell_words{MemTag::Network};
-  DeviceBuffer<uint64_t> cell_end{MemTag::Network}, scan_scratch{MemTag::Network};
-
-  // pass 1 and the scan; has synchronised on return
-  void measure(const Correction& corr, hipStream_t stream)
-  {
-    const CorrectionData& d = corr.data;
-    n = (uint32_t)d.cells.size();
-    verbatim = d.h.kind == kCorrectionVerbatim;
-    std::vector<CodeCell> host(n);
-    uint64_t codes = 0, group = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-      const uint64_t voxels = correction_cell_voxels(d.h.dims, d.cells[i].cell);
-      host[i] = CodeCell{corr.planes_uploaded ? (uint64_t)d.cells[i].cell : codes, (uint32_t)group, (uint32_t)voxels, d.cells[i].width};
-      codes += correction_padded_bytes(voxels, d.cells[i].width);
-      group += correction_cell_groups(voxels);
-    }
-    if (group > 0xffffffffull) throw std::runtime_error("the correction has more than 2^32 groups");
-    if (corr.planes_uploaded) src = CodeSource{nullptr, corr.d_plane_cells.ptr, corr.d_plane_groups.ptr, corr.d_planes()};
-    else src = CodeSource{corr.d_payload.ptr, nullptr, nullptr, nullptr};
-    cells.upload(host.data(), n, stream);
-    group_bits.resize(group);
-    cell_words.resize(n);
-    cell_end.resize(n);
-    correction_code_measure_kernel<<<cell_blocks(n), kWave, 0, stream>>>(src, cells.ptr, n, verbatim, group_bits.ptr, cell_words.ptr, cell_end.ptr);
-    VNR_HIP_CHECK(hipGetLastError());
-    device_inclusive_scan(cell_end.ptr, n, scan_scratch, stream);
-    VNR_HIP_CHECK(hipMemcpyAsync(&words, cell_end.ptr + (n - 1), sizeof(uint64_t), hipMemcpyDeviceToHost, stream));   // one count crosses to the host
-    VNR_HIP_CHECK(hipStreamSynchronize(stream));   // (`host` goes out of scope, too)
-    if (words > (uint64_t)n * kCodedMaxCellWords) throw std::runtime_error("internal error: the coded streams are longer than the format allows");
-  }
-  uint64_t payload_bytes() const { return correction_coded_table_bytes(n) + 8 * words; }
-  // pass 2: table, padding and streams at d_out (8-byte aligned, payload_bytes() of room); enqueued, not synchronised
-  void write(uint8_t* d_out, hipStream_t stream)
-  {
-    const uint64_t table_bytes = correction_coded_table_bytes(n);
-    VNR_HIP_CHECK(hipMemcpyAsync(d_out, cell_words.ptr, 4ull * n, hipMemcpyDeviceToDevice, stream));
-    if (table_bytes > 4ull * n) VNR_HIP_CHECK(hipMemsetAsync(d_out + 4ull * n, 0, table_bytes - 4ull * n, stream));
-    if (!words) return;
-    correction_code_write_kernel<<<cell_blocks(n), kWave, 0, stream>>>(src, cells.ptr, n, verbatim, group_bits.ptr, cell_end.ptr,
-                                                                       reinterpret_cast<uint64_t*>(d_out + table_bytes));
-    VNR_HIP_CHECK(hipGetLastError());
-  }
-};
-
-// the coded payload of a correction that holds nothing on the device, on the host
-std::vector<uint8_t> transcode_on_host(Correction& corr)
-{
-  const CorrectionData& d = corr.data;
-  if (corr.has_packed) return correction_coded_from_packed(d.h, d.cells, corr.packed_payload);
-  if (d.payload.empty()) throw std::runtime_error("internal error: the correction holds its codes neither on the host nor on the device");
-  return correction_coded_from_fixed(d.h, d.cells, d.payload);
-}
-
 }  // namespace
 
-const std::vector<uint8_t>& correction_coded_payload(Correction& corr, hipStream_t stream)
+void CorrectionEncoder::measure(const CorrectionHeader& h, const std::vector<CorrectionCellEntry>& entries, hipStream_t stream)
 {
-  if (corr.has_coded) return corr.coded_payload;
-  if (corr.data.cells.empty()) {   // no cell, no stream
-    corr.has_coded = true;
-    return corr.coded_payload;
-  }
-  if (!on_device(corr)) {
-    corr.coded_payload = transcode_on_host(corr);
-    corr.has_coded = true;
-    return corr.coded_payload;
-  }
-  Encoder enc;
-  enc.measure(corr, stream);
-  DeviceBuffer<uint8_t> d_out(MemTag::Network);
-  d_out.resize(enc.payload_bytes());
-  enc.write(d_out.ptr, stream);
-  std::vector<uint8_t> coded(enc.payload_bytes());
-  d_out.download(coded.data(), coded.size(), stream);   // (synchronises)
-  corr.coded_payload = std::move(coded);
-  corr.has_coded = true;
-  return corr.coded_payload;
+  n = (uint32_t)entries.size();
+  verbatim = h.kind == kCorrectionVerbatim;
+  const std::vector<CorrectionCellLayout> layout = correction_cell_layout(h, entries);
+  const uint64_t n_groups = n ? layout.back().group0 + layout.back().groups : 0;
+  if (n_groups > 0xffffffffull) throw std::runtime_error("the correction has more than 2^32 groups");
+  std::vector<CodeCell> host(n);
+  for (uint32_t i = 0; i < n; ++i) host[i] = CodeCell{d_codes ? layout[i].codes : (uint64_t)entries[i].cell, (uint32_t)layout[i].group0, layout[i].voxels, entries[i].width};
+  cells.upload(reinterpret_cast<const uint8_t*>(host.data()), n * sizeof(CodeCell), stream);
+  group_bits.resize(n_groups);
+  cell_words.resize(n);
+  cell_end.resize(n);
+  correction_code_measure_kernel<<<cell_blocks(n), kWave, 0, stream>>>(CodeSource{d_codes, d_plane_cells, d_plane_groups, d_planes}, reinterpret_cast<const CodeCell*>(cells.ptr), n,
+                                                                       verbatim, group_bits.ptr, cell_words.ptr, cell_end.ptr);
+  VNR_HIP_CHECK(hipGetLastError());
+  device_inclusive_scan(cell_end.ptr, n, scan_scratch, stream);
+  VNR_HIP_CHECK(hipMemcpyAsync(&words, cell_end.ptr + (n - 1), sizeof(uint64_t), hipMemcpyDeviceToHost, stream));   // one count crosses to the host
+  VNR_HIP_CHECK(hipStreamSynchronize(stream));   // (`host` goes out of scope, too)
+  if (words > (uint64_t)n * kCodedMaxCellWords) throw std::runtime_error("internal error: the coded streams are longer than the format allows");
 }
 
-void correction_serialize_coded_to_device(Correction& corr, void* d_bytes, size_t capacity, size_t* size, hipStream_t consumer)
+void CorrectionEncoder::write(uint8_t* d_out, hipStream_t stream)
 {
-  if (!size) throw std::runtime_error("null result");
-  const CorrectionData& d = corr.data;
-  hipStream_t stream = Runtime::get().stream;
-  Encoder enc;
-  const bool encode = !corr.has_coded && !d.cells.empty() && on_device(corr);   // else: the host copy, transcoded there if need be
-  if (encode) enc.measure(corr, stream);
-  const uint64_t payload_bytes = encode ? enc.payload_bytes() : correction_coded_payload(corr, stream).size();
-  std::vector<uint8_t> head = correction_coded_write(d.h, d.cells, std::vector<uint8_t>());
-  std::memcpy(head.data() + 80, &payload_bytes, sizeof(uint64_t));   // payload_bytes of the header (correction_format.h)
-  *size = head.size() + payload_bytes;
-  if (!d_bytes) return;
-  if (capacity < *size)
-    throw std::runtime_error("capacity (" + std::to_string(capacity) + " bytes) is smaller than the coded correction (" + std::to_string(*size) + " bytes)");
-  require_room(d_bytes, *size, "the coded bytes");
-  EventGuard ev;
-  wait_for(consumer, stream, ev);   // what the destination held may still be being read
-  uint8_t* d_payload = (uint8_t*)d_bytes + head.size();
-  DeviceBuffer<uint8_t> aligned(MemTag::Network);   // the kernel stores whole words: a destination off the 8-byte grid is reached by a copy
-  VNR_HIP_CHECK(hipMemcpyAsync(d_bytes, head.data(), head.size(), hipMemcpyHostToDevice, stream));
-  if (encode) {
-    if ((uintptr_t)d_payload % 8 == 0) {
-      enc.write(d_payload, stream);
-    } else {
-      aligned.resize(payload_bytes);
-      enc.write(aligned.ptr, stream);
-      VNR_HIP_CHECK(hipMemcpyAsync(d_payload, aligned.ptr, payload_bytes, hipMemcpyDeviceToDevice, stream));
-    }
-  } else if (payload_bytes) {
-    VNR_HIP_CHECK(hipMemcpyAsync(d_payload, corr.coded_payload.data(), payload_bytes, hipMemcpyHostToDevice, stream));
-  }
-  VNR_HIP_CHECK(hipStreamSynchronize(stream));   // on return the bytes are there; `head` and the encoder go out of scope
+  const uint64_t table_bytes = correction_coded_table_bytes(n);
+  VNR_HIP_CHECK(hipMemcpyAsync(d_out, cell_words.ptr, 4ull * n, hipMemcpyDeviceToDevice, stream));
+  if (table_bytes > 4ull * n) VNR_HIP_CHECK(hipMemsetAsync(d_out + 4ull * n, 0, table_bytes - 4ull * n, stream));
+  if (!words) return;
+  correction_code_write_kernel<<<cell_blocks(n), kWave, 0, stream>>>(CodeSource{d_codes, d_plane_cells, d_plane_groups, d_planes}, reinterpret_cast<const CodeCell*>(cells.ptr), n,
+                                                                     verbatim, group_bits.ptr, cell_end.ptr, reinterpret_cast<uint64_t*>(d_out + table_bytes));
+  VNR_HIP_CHECK(hipGetLastError());
 }
 
-void correction_decode_coded_on_device(Correction& corr, hipStream_t stream)
+void correction_decode_on_device(const CorrectionHeader& h, const std::vector<CorrectionCellEntry>& cells, const std::vector<uint8_t>& coded_payload,
+                                 const CorrectionPlaneIndex& ix, const uint32_t* d_plane_groups, uint64_t* d_planes, hipStream_t stream)
 {
-  const CorrectionData& d = corr.data;
-  const uint32_t n = (uint32_t)d.cells.size();
-  const uint64_t n_cells = correction_n_cells(d.h.dims), n_groups = corr.group_table.size();
-  const uint64_t table_bytes = correction_group_table_bytes(n_groups), coded_table = correction_coded_table_bytes(n);
-  if (n_groups != correction_n_groups(d.h, d.cells) || n_groups > 0xffffffffull || corr.coded_payload.size() < coded_table)
+  const uint32_t n = (uint32_t)cells.size();
+  const uint64_t coded_table = correction_coded_table_bytes(n);
+  if (ix.group_word.size() > 0xffffffffull || ix.cell_word0.size() != n || coded_payload.size() < coded_table)
     throw std::runtime_error("internal error: a coded correction without the group table of its parse");
-  // the index of the planes (what correction_plane_index gives for the packed payload) and the cells' places in both payloads
-  std::vector<Correction::PlaneCell> plane_cells(n_cells, Correction::PlaneCell{~0ull, 0, 0});
-  std::vector<uint32_t> groups(n_groups);
-  std::vector<DecodeCell> cells(n);
-  uint64_t g = 0, words = 0, stream0 = 0;
+  // the cells' places in both payloads
+  const std::vector<CorrectionCellLayout> layout = correction_cell_layout(h, cells);
+  std::vector<DecodeCell> host(n);
+  uint64_t stream0 = 0;
   for (uint32_t i = 0; i < n; ++i) {
-    const uint64_t voxels = correction_cell_voxels(d.h.dims, d.cells[i].cell), cell_groups = correction_cell_groups(voxels);
     uint32_t stream_words;
-    std::memcpy(&stream_words, corr.coded_payload.data() + 4ull * i, 4);
-    cells[i] = DecodeCell{stream0, words, stream_words, (uint32_t)g, (uint32_t)voxels, d.cells[i].width};
-    plane_cells[d.cells[i].cell] = Correction::PlaneCell{words, (uint32_t)g, 0};
-    uint32_t in_cell = 0;   // at most 64 groups of at most 64 planes
-    for (uint64_t k = 0; k < cell_groups; ++k, ++g) {
-      groups[g] = in_cell | (uint32_t)corr.group_table[g] << 16;
-      in_cell += corr.group_table[g];
-    }
-    words += in_cell;
+    std::memcpy(&stream_words, coded_payload.data() + 4ull * i, 4);
+    host[i] = DecodeCell{stream0, ix.cell_word0[i], stream_words, (uint32_t)ix.cell_group0[i], layout[i].voxels, cells[i].width};
     stream0 += stream_words;
   }
-  if (corr.coded_payload.size() != coded_table + 8 * stream0) throw std::runtime_error("internal error: the coded payload does not have the size its cell table gives");
+  if (coded_payload.size() != coded_table + 8 * stream0) throw std::runtime_error("internal error: the coded payload does not have the size its cell table gives");
   DeviceBuffer<uint8_t> d_coded(MemTag::Network);
   DeviceBuffer<DecodeCell> d_cells(MemTag::Network);
-  d_coded.upload(corr.coded_payload.data(), corr.coded_payload.size(), stream);   // as it is (hipMalloc aligns it; the streams start at a multiple of 8)
-  d_cells.upload(cells.data(), n, stream);
-  corr.d_plane_cells.upload(plane_cells.data(), plane_cells.size(), stream);
-  corr.d_plane_groups.upload(groups.data(), groups.size(), stream);
-  corr.d_packed.resize(table_bytes + 8 * words);
-  VNR_HIP_CHECK(hipMemsetAsync(corr.d_packed.ptr, 0, table_bytes, stream));   // (the table's padding)
-  VNR_HIP_CHECK(hipMemcpyAsync(corr.d_packed.ptr, corr.group_table.data(), n_groups, hipMemcpyHostToDevice, stream));
-  if (words) {
+  d_coded.upload(coded_payload.data(), coded_payload.size(), stream);   // as it is (hipMalloc aligns it; the streams start at a multiple of 8)
+  d_cells.upload(host.data(), n, stream);
+  if (ix.n_words) {
     correction_code_decode_kernel<<<cell_blocks(n), kWave, 0, stream>>>(reinterpret_cast<const uint64_t*>(d_coded.ptr + coded_table), d_cells.ptr, n,
-                                                                         d.h.kind == kCorrectionVerbatim, corr.d_plane_groups.ptr,
-                                                                         reinterpret_cast<uint64_t*>(corr.d_packed.ptr + table_bytes));
+                                                                         h.kind == kCorrectionVerbatim, d_plane_groups, d_planes);
     VNR_HIP_CHECK(hipGetLastError());
   }
-  VNR_HIP_CHECK(hipStreamSynchronize(stream));   // the stream has drained: the host vectors and the coded copy are released
-  corr.planes_uploaded = true;
+  VNR_HIP_CHECK(hipStreamSynchronize(stream));   // the stream has drained: the host vector and the coded copy are released
 }
 
 }  // namespace vnr

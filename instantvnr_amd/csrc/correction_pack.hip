@@ -8,17 +8,12 @@
 // the cell, and the cells' first words are the prefix sum of n_flagged small integers, taken on the host between the two pack kernels
 // (the codes never leave the device; tests/correction_pack_ref.py restates the format in numpy and is matched byte for byte).
 // Every offset is 64-bit.  The unpack runs the same walk backwards into a zeroed payload; the apply of correction.hip reads that.
-#include "volume.h"
-
-#include <algorithm>
+// The two launches at the end take what they work on as arguments: when they run and where the result is kept is correction_store.hip's.
+#include "correction_wave.h"
 
 namespace vnr {
 
 namespace {
-
-constexpr int kWave = 64;
-static_assert(kWave == (int)kCorrectionGroup, "a group is one wavefront");
-constexpr uint32_t kMaxBlocks = 1u << 20;   // cells beyond that are reached by block stride
 
 // a flagged cell in both forms
 struct PackCell {
@@ -26,23 +21,6 @@ struct PackCell {
   uint64_t group0;   // its first group in the group table
   uint32_t voxels, width;
 };
-
-__device__ __forceinline__ uint64_t wave_or(uint64_t v)
-{
-  for (int off = kWave / 2; off > 0; off >>= 1) v |= (uint64_t)__shfl_xor((unsigned long long)v, off, kWave);
-  return v;
-}
-
-// exclusive prefix sum over the lanes
-__device__ __forceinline__ uint32_t wave_exclusive_scan(uint32_t v, uint32_t lane)
-{
-  uint32_t incl = v;
-  for (int off = 1; off < kWave; off <<= 1) {
-    const uint32_t t = __shfl_up(incl, off, kWave);
-    if (lane >= (uint32_t)off) incl += t;
-  }
-  return incl - v;
-}
 
 // code i of a cell as the unsigned z of the packed form: the zigzag of the sign-extended code, or (verbatim) the bit pattern
 __device__ __forceinline__ uint64_t load_z(const uint8_t* __restrict__ codes, uint32_t width, uint32_t i, bool verbatim)
@@ -143,107 +121,48 @@ __global__ void __launch_bounds__(kWave) correction_unpack_kernel(const uint8_t*
   }
 }
 
-std::vector<PackCell> make_pack_cells(const CorrectionData& d)
+DeviceBuffer<PackCell> upload_pack_cells(const CorrectionHeader& h, const std::vector<CorrectionCellEntry>& cells, hipStream_t stream)
 {
-  std::vector<PackCell> cells(d.cells.size());
-  uint64_t codes = 0, group = 0;
-  for (size_t i = 0; i < cells.size(); ++i) {
-    const uint64_t voxels = correction_cell_voxels(d.h.dims, d.cells[i].cell);
-    cells[i] = PackCell{codes, group, (uint32_t)voxels, d.cells[i].width};
-    codes += correction_padded_bytes(voxels, d.cells[i].width);
-    group += correction_cell_groups(voxels);
-  }
-  return cells;
-}
-
-uint32_t cell_blocks(size_t n_cells) { return (uint32_t)std::min<size_t>(n_cells, kMaxBlocks); }
-
-// packed -> d_payload
-void unpack_on_device(Correction& corr, hipStream_t stream)
-{
-  const CorrectionData& d = corr.data;
-  // (a direct build: the group table has not been on the host yet; one decoded from coded bytes on the device has the parse's)
-  if (!corr.has_packed && !(corr.coded_pending() && corr.planes_uploaded)) correction_packed_payload(corr, stream);
-  const uint8_t* table = corr.has_packed ? corr.packed_payload.data() : corr.group_table.data();
-  const std::vector<PackCell> cells = make_pack_cells(d);
-  const uint64_t table_bytes = correction_group_table_bytes(correction_n_groups(d.h, d.cells));
-  // the cells' first plane words, from the table (validated when the bytes were read)
-  std::vector<uint64_t> word0(cells.size());
-  uint64_t words = 0;
-  for (size_t i = 0; i < cells.size(); ++i) {
-    word0[i] = words;
-    const uint64_t groups = correction_cell_groups(cells[i].voxels);
-    for (uint64_t k = 0; k < groups; ++k) words += table[cells[i].group0 + k];
-  }
-  if ((corr.has_packed ? corr.packed_payload.size() : corr.d_packed.bytes()) != table_bytes + 8 * words) throw std::runtime_error("the packed payload does not have the size its group table gives");
+  const std::vector<CorrectionCellLayout> layout = correction_cell_layout(h, cells);
+  std::vector<PackCell> host(cells.size());
+  for (size_t i = 0; i < host.size(); ++i) host[i] = PackCell{layout[i].codes, layout[i].group0, layout[i].voxels, cells[i].width};
   DeviceBuffer<PackCell> d_cells(MemTag::Network);
-  DeviceBuffer<uint64_t> d_word0(MemTag::Network);
-  DeviceBuffer<uint8_t> d_packed(MemTag::Network);
-  d_cells.upload(cells.data(), cells.size(), stream);
-  d_word0.upload(word0.data(), word0.size(), stream);
-  // as it is (hipMalloc aligns it; the planes start at a multiple of 8), unless the planes are resident already (the packed resident form)
-  if (!corr.planes_uploaded) d_packed.upload(corr.packed_payload.data(), corr.packed_payload.size(), stream);
-  const uint8_t* packed = corr.planes_uploaded ? corr.d_packed.ptr : d_packed.ptr;
-  corr.d_payload.resize(correction_fixed_payload_bytes(d.h, d.cells));
-  corr.d_payload.zero(stream);
-  correction_unpack_kernel<<<cell_blocks(cells.size()), kWave, 0, stream>>>(packed, reinterpret_cast<const uint64_t*>(packed + table_bytes), d_cells.ptr, d_word0.ptr,
-                                                                             (uint32_t)cells.size(), d.h.kind == kCorrectionVerbatim, corr.d_payload.ptr);
-  VNR_HIP_CHECK(hipGetLastError());
-  VNR_HIP_CHECK(hipStreamSynchronize(stream));   // the host vectors and the packed copy go out of scope
+  d_cells.upload(host.data(), host.size(), stream);
+  VNR_HIP_CHECK(hipStreamSynchronize(stream));   // `host` goes out of scope
+  return d_cells;
 }
 
 }  // namespace
 
-void correction_ensure_device_payload(Correction& corr, hipStream_t stream)
+void correction_unpack_on_device(const CorrectionHeader& h, const std::vector<CorrectionCellEntry>& cells, const uint8_t* table, const uint8_t* d_packed,
+                                 uint64_t packed_bytes, uint8_t* d_payload, hipStream_t stream)
 {
-  if (corr.uploaded || corr.payload_uploaded || corr.data.cells.empty()) return;
-  if (corr.from_packed || corr.direct || corr.planes_uploaded) {
-    unpack_on_device(corr, stream);
-  } else {
-    corr.d_payload.upload(corr.data.payload.data(), corr.data.payload.size(), stream);
-    VNR_HIP_CHECK(hipStreamSynchronize(stream));
-  }
-  corr.payload_uploaded = true;
+  const uint64_t n_groups = correction_n_groups(h, cells), table_bytes = correction_group_table_bytes(n_groups);
+  // the cells' first plane words, from the table (validated when the bytes were read)
+  const CorrectionPlaneIndex ix = correction_plane_index_of_table(h, cells, table, n_groups);
+  if (packed_bytes != table_bytes + 8 * ix.n_words) throw std::runtime_error("the packed payload does not have the size its group table gives");
+  const DeviceBuffer<PackCell> d_cells = upload_pack_cells(h, cells, stream);
+  DeviceBuffer<uint64_t> d_word0(MemTag::Network);
+  d_word0.upload(ix.cell_word0.data(), ix.cell_word0.size(), stream);
+  VNR_HIP_CHECK(hipMemsetAsync(d_payload, 0, correction_fixed_payload_bytes(h, cells), stream));
+  correction_unpack_kernel<<<cell_blocks(cells.size()), kWave, 0, stream>>>(d_packed, reinterpret_cast<const uint64_t*>(d_packed + table_bytes), d_cells.ptr, d_word0.ptr,
+                                                                             (uint32_t)cells.size(), h.kind == kCorrectionVerbatim, d_payload);
+  VNR_HIP_CHECK(hipGetLastError());
+  VNR_HIP_CHECK(hipStreamSynchronize(stream));   // the index and the scratch go out of scope
 }
 
-const std::vector<uint8_t>& correction_packed_payload(Correction& corr, hipStream_t stream)
+std::vector<uint8_t> correction_pack_on_device(const CorrectionHeader& h, const std::vector<CorrectionCellEntry>& cells, const uint8_t* d_payload, hipStream_t stream)
 {
-  if (corr.has_packed) return corr.packed_payload;
-  const CorrectionData& d = corr.data;
-  if (d.cells.empty()) {   // no group, no plane
-    corr.has_packed = true;
-    return corr.packed_payload;
-  }
-  if (corr.coded_pending()) {   // read from coded bytes: the planes as the device decoded them, downloaded once, or transcoded on the host
-    if (corr.planes_uploaded) {
-      corr.packed_payload.resize(corr.d_packed.count);
-      corr.d_packed.download(corr.packed_payload.data(), corr.d_packed.count, stream);   // (synchronises)
-      corr.has_packed = corr.from_packed = true;
-    } else {
-      corr.transcode_coded_on_host();
-    }
-    return corr.packed_payload;
-  }
-  if (corr.direct) {   // built straight into the planes: table and planes as they lie on the device, downloaded once
-    if (!corr.planes_uploaded) throw std::runtime_error("internal error: a direct correction holds its planes neither on the host nor on the device");
-    corr.packed_payload.resize(corr.d_packed.count);
-    corr.d_packed.download(corr.packed_payload.data(), corr.d_packed.count, stream);   // (synchronises)
-    corr.has_packed = true;
-    return corr.packed_payload;
-  }
-  correction_ensure_device_payload(corr, stream);
-  const std::vector<PackCell> cells = make_pack_cells(d);
   const uint32_t n = (uint32_t)cells.size();
-  const uint64_t table_bytes = correction_group_table_bytes(correction_n_groups(d.h, d.cells));
-  const bool verbatim = d.h.kind == kCorrectionVerbatim;
-  DeviceBuffer<PackCell> d_cells(MemTag::Network);
+  const uint64_t table_bytes = correction_group_table_bytes(correction_n_groups(h, cells));
+  const bool verbatim = h.kind == kCorrectionVerbatim;
+  const DeviceBuffer<PackCell> d_cells = upload_pack_cells(h, cells, stream);
   DeviceBuffer<uint8_t> d_table(MemTag::Network);
   DeviceBuffer<uint32_t> d_cell_words(MemTag::Network);
-  d_cells.upload(cells.data(), n, stream);
   d_table.resize(table_bytes);
   d_table.zero(stream);   // (its padding)
   d_cell_words.resize(n);
-  correction_pack_measure_kernel<<<cell_blocks(n), kWave, 0, stream>>>(corr.d_payload.ptr, d_cells.ptr, n, verbatim, d_table.ptr, d_cell_words.ptr);
+  correction_pack_measure_kernel<<<cell_blocks(n), kWave, 0, stream>>>(d_payload, d_cells.ptr, n, verbatim, d_table.ptr, d_cell_words.ptr);
   VNR_HIP_CHECK(hipGetLastError());
   // the cells' first words: n_flagged small integers through the host
   std::vector<uint32_t> cell_words(n);
@@ -256,14 +175,12 @@ const std::vector<uint8_t>& correction_packed_payload(Correction& corr, hipStrea
   d_word0.upload(word0.data(), n, stream);
   if (words) {
     d_planes.resize(words);
-    correction_pack_planes_kernel<<<cell_blocks(n), kWave, 0, stream>>>(corr.d_payload.ptr, d_cells.ptr, d_word0.ptr, n, verbatim, d_table.ptr, d_planes.ptr);
+    correction_pack_planes_kernel<<<cell_blocks(n), kWave, 0, stream>>>(d_payload, d_cells.ptr, d_word0.ptr, n, verbatim, d_table.ptr, d_planes.ptr);
     VNR_HIP_CHECK(hipGetLastError());
     VNR_HIP_CHECK(hipMemcpyAsync(packed.data() + table_bytes, d_planes.ptr, 8 * words, hipMemcpyDeviceToHost, stream));
   }
   d_table.download(packed.data(), table_bytes, stream);   // (synchronises)
-  corr.packed_payload = std::move(packed);
-  corr.has_packed = true;
-  return corr.packed_payload;
+  return packed;
 }
 
 }  // namespace vnr

@@ -39,6 +39,20 @@ uint64_t lane_mask(uint64_t voxels, uint64_t k)
 
 }  // namespace
 
+std::vector<CorrectionCellLayout> correction_cell_layout(const CorrectionHeader& h, const std::vector<CorrectionCellEntry>& cells)
+{
+  std::vector<CorrectionCellLayout> out;
+  out.reserve(cells.size());
+  uint64_t codes = 0, group = 0;
+  for (const CorrectionCellEntry& e : cells) {
+    const uint64_t voxels = correction_cell_voxels(h.dims, e.cell), groups = correction_cell_groups(voxels);
+    out.push_back(CorrectionCellLayout{codes, group, (uint32_t)voxels, (uint32_t)groups});
+    codes += correction_padded_bytes(voxels, e.width);
+    group += groups;
+  }
+  return out;
+}
+
 uint64_t correction_n_groups(const CorrectionHeader& h, const std::vector<CorrectionCellEntry>& cells)
 {
   uint64_t n = 0;
@@ -195,28 +209,32 @@ std::vector<uint8_t> correction_unpack(const CorrectionHeader& h, const std::vec
   return out;
 }
 
-CorrectionPlaneIndex correction_plane_index(const CorrectionHeader& h, const std::vector<CorrectionCellEntry>& cells, const std::vector<uint8_t>& packed_payload)
+CorrectionPlaneIndex correction_plane_index_of_table(const CorrectionHeader& h, const std::vector<CorrectionCellEntry>& cells, const uint8_t* table, uint64_t n_groups)
 {
   CorrectionPlaneIndex ix;
-  const uint64_t n_groups = correction_n_groups(h, cells), table_bytes = correction_group_table_bytes(n_groups);
-  if (packed_payload.size() < table_bytes) throw std::runtime_error("the packed payload is shorter than its group table");
   ix.cell_group0.reserve(cells.size());
   ix.cell_word0.reserve(cells.size());
   ix.group_word.reserve(n_groups);
-  const uint8_t* table = packed_payload.data();
-  uint64_t g = 0;
-  for (const CorrectionCellEntry& e : cells) {
-    const uint64_t groups = correction_cell_groups(correction_cell_voxels(h.dims, e.cell));
-    ix.cell_group0.push_back(g);
+  for (const CorrectionCellLayout& c : correction_cell_layout(h, cells)) {
+    if (c.group0 + c.groups > n_groups) throw std::runtime_error("the group table is shorter than the cells' groups");
+    ix.cell_group0.push_back(c.group0);
     ix.cell_word0.push_back(ix.n_words);
     uint32_t in_cell = 0;   // at most 64 groups of at most 64 planes
-    for (uint64_t k = 0; k < groups; ++k, ++g) {
+    for (uint64_t g = c.group0; g < c.group0 + c.groups; ++g) {
       if (table[g] > kCorrectionGroup) throw std::runtime_error("nbits " + std::to_string(table[g]) + " of group " + std::to_string(g) + " exceeds 64");
       ix.group_word.push_back((uint16_t)in_cell);
       in_cell += table[g];
     }
     ix.n_words += in_cell;
   }
+  return ix;
+}
+
+CorrectionPlaneIndex correction_plane_index(const CorrectionHeader& h, const std::vector<CorrectionCellEntry>& cells, const std::vector<uint8_t>& packed_payload)
+{
+  const uint64_t n_groups = correction_n_groups(h, cells), table_bytes = correction_group_table_bytes(n_groups);
+  if (packed_payload.size() < table_bytes) throw std::runtime_error("the packed payload is shorter than its group table");
+  CorrectionPlaneIndex ix = correction_plane_index_of_table(h, cells, packed_payload.data(), n_groups);
   if (packed_payload.size() - table_bytes != 8 * ix.n_words) throw std::runtime_error("the packed payload does not have the size its group table gives");
   return ix;
 }

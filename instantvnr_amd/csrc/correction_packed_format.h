@@ -30,6 +30,15 @@ inline uint64_t correction_group_table_bytes(uint64_t n_groups) { return (n_grou
 // the payload size of the fixed-width form: the sum of the padded cell sizes
 uint64_t correction_fixed_payload_bytes(const CorrectionHeader& h, const std::vector<CorrectionCellEntry>& cells);
 
+// Where a flagged cell lies in the fixed-width payload and in the group table: the one walk over the entries that every form's
+// offsets start from (the entries must be ones a reader accepted or a build made)
+struct CorrectionCellLayout {
+  uint64_t codes;    // byte offset of its codes in the fixed-width payload (a multiple of 16)
+  uint64_t group0;   // its first group in the group table
+  uint32_t voxels, groups;
+};
+std::vector<CorrectionCellLayout> correction_cell_layout(const CorrectionHeader& h, const std::vector<CorrectionCellEntry>& cells);
+
 std::vector<uint8_t> correction_packed_write(const CorrectionHeader& h, const std::vector<CorrectionCellEntry>& cells, const std::vector<uint8_t>& payload);
 // throws std::runtime_error("malformed packed correction bytes: <rule>"); everything is validated before anything is allocated by the
 // bytes' say.  What it accepts, correction_packed_write gives back byte for byte.
@@ -45,6 +54,9 @@ struct CorrectionPlaneIndex {
   std::vector<uint16_t> group_word;                // per group: the plane words of its cell in front of it, at most 63 * 64
   uint64_t n_words = 0;                            // plane words in all
 };
+// from a group table alone (one byte nbits per group, without padding: a packed payload's first bytes, or the coded parse's
+// by-product); throws if n_groups is less than the entries' or an nbits exceeds 64
+CorrectionPlaneIndex correction_plane_index_of_table(const CorrectionHeader& h, const std::vector<CorrectionCellEntry>& cells, const uint8_t* table, uint64_t n_groups);
 // of a packed payload that correction_packed_parse accepted or the device pack made; throws if the payload's size is not the one its
 // group table gives
 CorrectionPlaneIndex correction_plane_index(const CorrectionHeader& h, const std::vector<CorrectionCellEntry>& cells, const std::vector<uint8_t>& packed_payload);

@@ -9,8 +9,6 @@
 #include <memory>
 
 #include "common.h"
-#include "correction_format.h"
-#include "correction_packed_format.h"
 #include "correction_coded_format.h"
 #include "json.h"
 #include "network.h"
@@ -112,82 +110,7 @@ struct DecodeError {
   double sum_abs, sum_sq, psnr_db;
 };
 
-// An error-bound correction (correction.hip; vnrAmdCorrection of include/vnr_amd.h): the serialisable part on the host, the report of the
-// build that made it, and the device copies the apply reads (a correction loaded from bytes uploads them at its first use).
-struct CorrectionTableEntry { uint64_t offset; uint32_t width, pad; };   // per macrocell: byte offset of its codes in the payload, or ~0
-struct Correction {
-  CorrectionData data;
-  uint64_t n_voxels_flagged = 0, n_nan = 0;
-  double max_abs_before = 0.0;
-  int worst_after[3] = {-1, -1, -1};
-  DeviceBuffer<uint8_t> d_payload{MemTag::Network};
-  DeviceBuffer<CorrectionTableEntry> d_table{MemTag::Network};
-  bool uploaded = false;
-  // The packed form (correction_packed_format.h, correction_pack.hip).  packed_payload: the group table and the planes, either what the
-  // correction was read from (from_packed) or the cached result of the device pack (a correction never changes).  A correction read
-  // from packed bytes has an empty data.payload until the host unpacks it (host_payload), and d_payload is unpacked on the device.
-  std::vector<uint8_t> packed_payload;
-  bool has_packed = false, from_packed = false;
-  bool payload_uploaded = false;   // d_payload holds the fixed-width payload although the table is not there yet (`uploaded` implies it)
-  // The resident form (vnrAmdCorrectionSetResidentForm): what the apply reads on the device.  0, fixed: d_table and d_payload above.
-  // 1, packed: the packed payload as it is serialised and the index correction_plane_index gives, {first plane word, first group} for
-  // every cell of the grid and {first word inside the cell, nbits} for every group; d_table and d_payload are then released.
-  struct PlaneCell { uint64_t word0; uint32_t group0, pad; };   // word0 = ~0: the cell is not flagged
-  int resident_form = 0;
-  DeviceBuffer<uint8_t> d_packed{MemTag::Network};
-  DeviceBuffer<PlaneCell> d_plane_cells{MemTag::Network};
-  DeviceBuffer<uint32_t> d_plane_groups{MemTag::Network};   // word | nbits << 16
-  bool planes_uploaded = false;
-  // Built straight into the planes (NeuralVolume::build_correction_packed): d_packed and the index came from the device, there is no
-  // fixed-width payload anywhere and packed_payload is empty until correction_packed_payload downloads d_packed (has_packed); from
-  // then on the correction behaves like one read from packed bytes.
-  bool direct = false;
-  // The coded form (correction_coded_format.h, correction_code.hip).  coded_payload: the cell table and the streams, either what the
-  // correction was read from (from_coded) or the cached result of vnrAmdCorrectionSerializeCoded.  A correction read from coded bytes
-  // holds nothing else until its first use: on the host alone it is transcoded into packed_payload there (from then on it behaves like
-  // one read from packed bytes); at a first use on the device the streams are decoded into d_packed there, and the host takes the
-  // packed payload from there when it first needs it.  group_table is the parse's by-product, the packed form's nbits of every group.
-  std::vector<uint8_t> coded_payload, group_table;
-  bool has_coded = false, from_coded = false;
-  bool coded_pending() const { return from_coded && !has_packed; }   // the host holds no packed payload yet
-  void transcode_coded_on_host()
-  {
-    if (!coded_pending()) return;
-    packed_payload = correction_coded_to_packed(data.h, data.cells, coded_payload, group_table);
-    has_packed = from_packed = true;
-  }
-  const uint64_t* d_planes() const { return reinterpret_cast<const uint64_t*>(d_packed.ptr + correction_group_table_bytes(d_plane_groups.count)); }
-  const std::vector<uint8_t>& host_payload()   // data.payload, unpacked on the host at its first use (direct: has_packed comes first)
-  {
-    transcode_coded_on_host();
-    if ((from_packed || (direct && has_packed)) && data.payload.empty() && !data.cells.empty()) data.payload = correction_unpack(data.h, data.cells, packed_payload);
-    return data.payload;
-  }
-};
-
-// correction_pack.hip.  The fixed-width payload made resident in d_payload: uploaded, or (from_packed, or with the planes resident)
-// unpacked from the packed payload on the device; and the device pack into packed_payload, which makes the payload resident first.
-// Both have synchronised on return.
-void correction_ensure_device_payload(Correction& corr, hipStream_t stream);
-const std::vector<uint8_t>& correction_packed_payload(Correction& corr, hipStream_t stream);
-// What the apply of corr.resident_form reads made resident, and what only the other form reads released once the stream has drained.
-// Has synchronised on return.  A correction without a flagged cell holds nothing.
-void correction_make_resident(Correction& corr, hipStream_t stream);
-// vnrAmdCorrectionSetResidentForm: a correction that holds nothing on the device only notes the form, any other is converted at once
-void correction_set_resident_form(Correction& corr, int form, hipStream_t stream);
-// vnrAmdCorrectionSerializePackedToDevice: the "VNRCORP1" bytes into device memory, header and entries from the host, table and planes
-// device to device (made resident in the current form's way first).  d_bytes null: only *size.  Returns after completion.
-void correction_serialize_packed_to_device(Correction& corr, void* d_bytes, size_t capacity, size_t* size, hipStream_t consumer);
-// correction_code.hip.  The coded payload (cell table and streams): encoded on the device from whichever form is resident, no code or
-// plane crossing to the host, or, for a correction that holds nothing on the device, transcoded on the host without asking for one;
-// cached in coded_payload.  Has synchronised on return.
-const std::vector<uint8_t>& correction_coded_payload(Correction& corr, hipStream_t stream);
-// vnrAmdCorrectionSerializeCodedToDevice: the "VNRCORC1" bytes into device memory, encoded there straight into the destination (from
-// the host copy where the correction holds nothing on the device).  d_bytes null: only *size.  Returns after completion.
-void correction_serialize_coded_to_device(Correction& corr, void* d_bytes, size_t capacity, size_t* size, hipStream_t consumer);
-// the first use on the device of a correction read from coded bytes: the streams uploaded as they are and decoded by one kernel into
-// the packed resident form (d_packed and its index, as correction_make_resident leaves them); the coded copy on the device is released
-void correction_decode_coded_on_device(Correction& corr, hipStream_t stream);
+struct Correction;   // an error-bound correction: correction_record.h (what it holds), correction_store.hip (its conversions)
 
 // guided_sampler.hip: the hierarchical inclusive scan of n uint64 in place (block scans, the block sums scanned the same way level by
 // level, offsets added on the way down); scratch is grown to the upper levels' size.  Enqueued on s, not synchronised.

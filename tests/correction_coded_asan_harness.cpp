@@ -42,6 +42,15 @@ int main(int argc, char** argv)
     if (vnr::correction_coded_from_packed(c.h, c.cells, packed) != c.payload) { std::fprintf(stderr, "packed -> coded differs\n"); return 4; }
     if (vnr::correction_coded_from_fixed(c.h, c.cells, vnr::correction_unpack(c.h, c.cells, packed)) != c.payload) { std::fprintf(stderr, "fixed -> coded differs\n"); return 4; }
     if (vnr::correction_coded_write(c.h, c.cells, c.payload) != in) { std::fprintf(stderr, "round trip differs\n"); return 4; }
+    // the parse's group table alone gives the index of the planes the device decode writes: the one of the transcoded payload
+    const vnr::CorrectionPlaneIndex ix = vnr::correction_plane_index_of_table(c.h, c.cells, c.group_nbits.data(), c.group_nbits.size());
+    const vnr::CorrectionPlaneIndex whole = vnr::correction_plane_index(c.h, c.cells, packed);
+    const std::vector<vnr::CorrectionCellLayout> layout = vnr::correction_cell_layout(c.h, c.cells);
+    if (ix.cell_group0 != whole.cell_group0 || ix.cell_word0 != whole.cell_word0 || ix.group_word != whole.group_word || ix.n_words != whole.n_words ||
+        layout.size() != c.cells.size() || (!layout.empty() && layout.back().group0 + layout.back().groups != c.group_nbits.size())) {
+      std::fprintf(stderr, "layout or index differs\n");
+      return 4;
+    }
     ++n_ok;
   }
   std::printf("%zu parsed, %zu refused\n", n_ok, n_err);

@@ -38,6 +38,20 @@ int main(int argc, char** argv)
     const std::vector<uint8_t> fixed = vnr::correction_write(v1);
     if (vnr::correction_parse(fixed.data(), fixed.size()).payload != v1.payload) { std::fprintf(stderr, "fixed-width round trip differs\n"); return 4; }
     if (vnr::correction_packed_write(p.h, p.cells, p.payload) != in) { std::fprintf(stderr, "round trip differs\n"); return 4; }
+    // the one layout walk and the index from the group table alone: their ends are the sizes of both payloads, and the index of the
+    // whole payload is the same index
+    const std::vector<vnr::CorrectionCellLayout> layout = vnr::correction_cell_layout(p.h, p.cells);
+    const uint64_t n_groups = vnr::correction_n_groups(p.h, p.cells);
+    const vnr::CorrectionPlaneIndex ix = vnr::correction_plane_index_of_table(p.h, p.cells, p.payload.data(), n_groups);
+    const vnr::CorrectionPlaneIndex whole = vnr::correction_plane_index(p.h, p.cells, p.payload);
+    bool same = layout.size() == p.cells.size() && ix.cell_group0 == whole.cell_group0 && ix.cell_word0 == whole.cell_word0 && ix.group_word == whole.group_word &&
+                p.payload.size() == vnr::correction_group_table_bytes(n_groups) + 8 * ix.n_words;
+    for (size_t i = 0; same && i < layout.size(); ++i) {
+      const uint64_t next_codes = i + 1 < layout.size() ? layout[i + 1].codes : v1.payload.size(), next_group = i + 1 < layout.size() ? layout[i + 1].group0 : n_groups;
+      same = layout[i].group0 == ix.cell_group0[i] && layout[i].group0 + layout[i].groups == next_group &&
+             layout[i].codes + vnr::correction_padded_bytes(layout[i].voxels, p.cells[i].width) == next_codes;
+    }
+    if (!same) { std::fprintf(stderr, "layout or index differs\n"); return 4; }
     ++n_ok;
   }
   std::printf("%zu parsed, %zu refused\n", n_ok, n_err);

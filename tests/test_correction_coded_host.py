@@ -5,6 +5,7 @@ correction that holds nothing on the device) agree with it byte for byte, every 
 is smaller than the packed one where it was built to be, and reader, transcoders and writer run under address / undefined-behaviour
 sanitizers in a stand-alone program.  CPU only; every comparison has tolerance zero."""
 import ctypes as C
+import itertools
 import math
 import os
 import struct
@@ -112,6 +113,44 @@ def test_a_correction_without_a_flagged_cell_codes_on_the_host():
     assert api.Correction.from_bytes(v1).to_coded_bytes() == coded
     c = api.Correction.from_coded_bytes(coded)
     assert c.to_bytes() == v1 and c.to_packed_bytes() == cpr.pack(v1) and c.to_coded_bytes() == coded
+
+
+def small_blobs():
+    """(name, fixed-width bytes): the blobs crafted for the packed and the coded form, and a correction without a flagged cell"""
+    dec = np.zeros((3, 4, 5), np.float32)
+    out = [(f"crafted-{t.__name__}-{e}-w{w}", cases.crafted(t, e, w)[0]) for t, e, w in cases.CRAFTED] + ccc.crafted()
+    return out + [("empty", ebr.build(dec, dec, 0.5, None)["bytes"])]
+
+
+@pytest.mark.parametrize("name,v1", small_blobs(), ids=[b[0] for b in small_blobs()])
+def test_every_order_of_the_serialisers_stays_on_the_host(name, v1):
+    """a correction read from bytes and never applied answers every serialisation, every size query and info() without a device,
+    whichever conversion comes first: each of the six orders on ONE object, whose caches fill up, and on a fresh one per order"""
+    want = {"to_bytes": v1, "to_packed_bytes": cpr.pack(v1), "to_coded_bytes": ccr.encode(v1)}
+    f, cells, _ = cpr.split(v1, b"VNRCORR1")
+    info = api.Correction.from_bytes(v1).info()
+    assert (info["payload_bytes"], info["serialized_bytes"], info["n_flagged"]) == (f[15], len(v1), len(cells))
+
+    def run(c, order, sizes=("to_packed_device", "to_coded_device")):
+        for call in order:
+            assert getattr(c, call)() == want[call], (order, call)
+            for size in sizes:
+                assert getattr(c, size)() == len(want[size.replace("device", "bytes")]), (order, call, size)   # (None: the size alone)
+            assert same_info(c.info(), info) and not c.residency()["on_device"], (order, call)
+
+    for read, form in ((api.Correction.from_packed_bytes, "to_packed_bytes"), (api.Correction.from_coded_bytes, "to_coded_bytes")):
+        one = read(want[form])
+        for order in itertools.permutations(want):
+            run(one, order)
+            fresh = read(want[form])
+            run(fresh, order)
+            fresh.release()
+        one.release()
+    # read from fixed-width bytes: its packed form is the device pack's; everything else is the host's
+    for order in itertools.permutations(("to_bytes", "to_coded_bytes")):
+        c = api.Correction.from_bytes(v1)
+        run(c, order, sizes=("to_coded_device",))
+        c.release()
 
 
 # ------------------------------------------------------------------------------------------------ the size statement

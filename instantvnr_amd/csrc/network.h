@@ -6,6 +6,7 @@
 #pragma once
 
 #include <functional>
+#include <memory>
 #include <utility>
 #include <vector>
 
@@ -88,6 +89,10 @@ static_assert(sizeof(OptState) == 16, "OptState must be one 16-byte record");
 struct TileNet;
 struct PackArgs;   // infer_tile.h: what a kernel needs to evaluate the network itself
 struct FusedMlp;   // infer_kernel.h: weight image + shape of a launch
+
+// the training step's buffers that need no place in the class interface: defined in network_train.hip, owned by the network
+struct TrainScratch;
+struct TrainScratchDeleter { void operator()(TrainScratch* p) const; };
 
 struct GradExchange {
   virtual ~GradExchange() = default;
@@ -249,6 +254,7 @@ private:
   const LevelInfo* inference_levels(hipStream_t s, const uint8_t** image, size_t n_max) const;  // decides / builds / orders streams
   void build_brick_image(hipStream_t s, bool small) const;
   static double brick_small_budget();
+  TrainScratch& train_scratch() const;   // created on first use
 
   ModelConfig cfg_;
   Json model_;
@@ -274,6 +280,7 @@ private:
   DeviceBuffer<uint16_t> ws_dfeat_{MemTag::Network};     // [B][in_width] dL/dfeatures (fp16, loss-scaled)
   DeviceBuffer<float> ws_loss_{MemTag::Network};         // [blocks] partial loss sums
   size_t ws_batch_ = 0;
+  mutable std::unique_ptr<TrainScratch, TrainScratchDeleter> train_;   // (mutable: training_buffer is const and may be the first to ask)
   // training step: weight gradients + the dense levels' LDS scatter beside the atomic scatter (network_train.hip forward_backward)
   hipStream_t side_stream_ = nullptr;
   hipEvent_t ev_fork_ = nullptr, ev_join_ = nullptr;

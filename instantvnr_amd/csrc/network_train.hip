@@ -9,6 +9,10 @@
 // precision; packed fp16 atomics), so a data-parallel run exchanges a single tensor; the MLP backward and the weight gradients run on MFMA
 // with the forward's transposed register-resident scheme; the dense coarse levels scatter through LDS tiles; since round 5 the weight
 // gradients and that LDS scatter run on a side stream beside a persistent atomic scatter of the hashed levels.
+#include <mutex>
+#include <set>
+#include <type_traits>
+
 #include "infer_kernel.h"
 
 namespace vnr {
@@ -518,17 +522,15 @@ __global__ void fold_grid_grads_f32_kernel(float* __restrict__ image, half_t* __
 // with the x bit 0.242, packed fp16 pairs 0.242: DESIGN.md 4.3), so what matters is that the lanes of one entry pair are adjacent:
 // the x-neighbour of a corner is the adjacent table entry on dense levels and, for even x, on hashed levels ((x+1)^h = (x^h)^1).
 // Every lane repeats the (cheap) index arithmetic of its sample.
+template <int F> struct GridLanes { static constexpr uint32_t pairs = F >= 2 ? (uint32_t)F / 2u : 1u, per_sample = 2u * pairs; };
+
+// One lane of the plain and of the persistent form: lane r of sample i, from the gradient load to the last atomic.
 template <int F>
-__global__ void grid_backward_kernel(const GridDevice grid, const float* __restrict__ coords, const half_t* __restrict__ dfeat,
-                                     uint32_t n, uint32_t in_width, typename GridGrad<F>::type* __restrict__ grid_grads, uint32_t level0)
+__device__ __forceinline__ void grid_backward_lane(const GridDevice& grid, const float* __restrict__ coords, const half_t* __restrict__ dfeat,
+                                                   uint32_t in_width, typename GridGrad<F>::type* __restrict__ grid_grads, uint32_t level, uint32_t i, uint32_t r)
 {
-  constexpr uint32_t P = F >= 2 ? (uint32_t)F / 2u : 1u;   // packed pairs per entry
-  constexpr uint32_t kLanesPerSample = 2u * P;
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t i = t / kLanesPerSample, r = t % kLanesPerSample;
+  constexpr uint32_t P = GridLanes<F>::pairs;   // packed pairs per entry
   const uint32_t xb = r / P, f = 2u * (r % P);
-  if (i >= n) return;
-  const uint32_t level = level0 + blockIdx.y;
   const LevelInfo lv = grid.levels[level];
   float g0, g1 = 0.0f;
   if constexpr (F >= 2) {
@@ -560,54 +562,33 @@ __global__ void grid_backward_kernel(const GridDevice grid, const float* __restr
   }
 }
 
+template <int F>
+__global__ void grid_backward_kernel(const GridDevice grid, const float* __restrict__ coords, const half_t* __restrict__ dfeat,
+                                     uint32_t n, uint32_t in_width, typename GridGrad<F>::type* __restrict__ grid_grads, uint32_t level0)
+{
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t i = t / GridLanes<F>::per_sample, r = t % GridLanes<F>::per_sample;
+  if (i >= n) return;
+  grid_backward_lane<F>(grid, coords, dfeat, in_width, grid_grads, level0 + blockIdx.y, i, r);
+}
+
 // The same scatter as a PERSISTENT grid of a few blocks per CU that walks (level, lane) work items: memory-side atomics are issued without
 // waiting for them, so a handful of waves per CU already saturates the chip's atomic request rate, and the rest of the CU stays free for
 // the kernels that run beside it on the side stream (weight gradients, the dense levels' LDS scatter: forward_backward).  The plain
 // kernel's grid of one block per 256 lanes takes every wave slot of the GPU while it lasts, which is why running those kernels beside it
-// bought nothing in round 4.  Per lane the arithmetic is grid_backward_kernel's, statement for statement.
+// bought nothing in round 4.
 template <int F>
 __global__ void __launch_bounds__(256) grid_backward_persistent_kernel(const GridDevice grid, const float* __restrict__ coords, const half_t* __restrict__ dfeat,
                                                                        uint32_t n, uint32_t in_width, typename GridGrad<F>::type* __restrict__ grid_grads, uint32_t level0, uint32_t n_levels)
 {
-  constexpr uint32_t P = F >= 2 ? (uint32_t)F / 2u : 1u;
-  constexpr uint32_t kLanesPerSample = 2u * P;
-  const uint32_t per_level = (n * kLanesPerSample + 255u) & ~255u;          // lanes of one level, whole blocks: the level is uniform over a block's trip
+  const uint32_t per_level = (n * GridLanes<F>::per_sample + 255u) & ~255u;   // lanes of one level, whole blocks: the level is uniform over a block's trip
   const uint64_t total = (uint64_t)per_level * n_levels;
-  const bool nearest = grid.interpolation == 2u;
   for (uint64_t w = (uint64_t)blockIdx.x * 256u + threadIdx.x; w < total; w += (uint64_t)gridDim.x * 256u) {
     const uint32_t level = level0 + (uint32_t)(w / per_level);
     const uint32_t t = (uint32_t)(w % per_level);
-    const uint32_t i = t / kLanesPerSample, r = t % kLanesPerSample;
-    const uint32_t xb = r / P, f = 2u * (r % P);
+    const uint32_t i = t / GridLanes<F>::per_sample, r = t % GridLanes<F>::per_sample;
     if (i >= n) continue;
-    const LevelInfo lv = grid.levels[level];
-    float g0, g1 = 0.0f;
-    if constexpr (F >= 2) {
-      const half2_t g2 = *(const half2_t*)(dfeat + (size_t)i * in_width + level * F + f);
-      g0 = (float)g2[0]; g1 = (float)g2[1];
-    } else {
-      g0 = (float)dfeat[(size_t)i * in_width + level];
-    }
-    if (g0 == 0.0f && g1 == 0.0f) continue;
-    if (nearest && xb) continue;
-    const CornerSetup c = level_setup(lv, grid.interpolation == 1u ? 1u : 0u, coords[3 * (size_t)i], coords[3 * (size_t)i + 1], coords[3 * (size_t)i + 2]);
-    auto* base = grid_grads + (size_t)lv.offset * F + (F >= 2 ? f : 0u);
-#pragma unroll
-    for (int yz = 0; yz < 4; ++yz) {
-      if (nearest && yz) break;
-      const int corner = (int)xb | (yz << 1);
-      const uint32_t idx = level_index(lv, c.g[0] + xb, c.g[1] + (uint32_t)(yz & 1), c.g[2] + (uint32_t)(yz >> 1));
-      const float wgt = nearest ? 1.0f : corner_weight(c, corner);
-      if constexpr (F >= 2) {
-        const half2_t v = half2_t{(half_t)(wgt * g0), (half_t)(wgt * g1)};
-        half_t* addr = base + (size_t)idx * F;
-        asm volatile("global_atomic_pk_add_f16 %0, %1, off" : : "v"(addr), "v"(v) : "memory");
-      } else {
-        const float v = wgt * g0;
-        float* addr = base + idx;
-        asm volatile("global_atomic_add_f32 %0, %1, off" : : "v"(addr), "v"(v) : "memory");
-      }
-    }
+    grid_backward_lane<F>(grid, coords, dfeat, in_width, grid_grads, level, i, r);
   }
 }
 
@@ -621,15 +602,14 @@ __global__ void __launch_bounds__(256) grid_backward_persistent_kernel(const Gri
 // keep the global-atomic kernel.
 struct LdsBwdItem { uint32_t level, e0, e1, s0, s1; };   // entries [e0, e1) of `level`, samples [s0, s1)
 
-template <int F>
-__global__ void __launch_bounds__(256) grid_backward_lds_kernel(const GridDevice grid, const LdsBwdItem* __restrict__ items, const float* __restrict__ coords,
-                                                                const half_t* __restrict__ dfeat, uint32_t in_width, typename GridGrad<F>::type* __restrict__ grid_grads)
+// The walk of one work item, shared by the production and the deterministic kernel: clears the tile's n_acc accumulators, then calls
+// add(slot, f, w, g_f) for every corner of the slice's samples that falls into the tile (slot = entry - e0; g_f = dL/dfeature f of the sample,
+// which may be zero when another feature of the sample is not).  The tile is complete for the whole block on return.
+template <int F, class Acc, class Add>
+__device__ __forceinline__ void lds_tile_walk(const GridDevice& grid, const LdsBwdItem& it, const LevelInfo& lv, const float* __restrict__ coords,
+                                              const half_t* __restrict__ dfeat, uint32_t in_width, Acc* s_acc, uint32_t n_acc, Add add)
 {
-  extern __shared__ float s_acc[];   // [e1 - e0][F]
-  const LdsBwdItem it = items[blockIdx.x];
-  const LevelInfo lv = grid.levels[it.level];
-  const uint32_t n_acc = (it.e1 - it.e0) * (uint32_t)F;
-  for (uint32_t e = threadIdx.x; e < n_acc; e += blockDim.x) s_acc[e] = 0.0f;
+  for (uint32_t e = threadIdx.x; e < n_acc; e += blockDim.x) s_acc[e] = Acc(0);
   __syncthreads();
   const bool nearest = grid.interpolation == 2u;
   // A tile is a contiguous entry range of a dense level, i.e. a slab of grid z; a sample's eight corners have z in {gz, gz + 1}, so all of
@@ -660,10 +640,22 @@ __global__ void __launch_bounds__(256) grid_backward_lds_kernel(const GridDevice
       if (idx < it.e0 || idx >= it.e1) continue;
       const float w = nearest ? 1.0f : corner_weight(c, corner);
 #pragma unroll
-      for (int f = 0; f < F; ++f) atomicAdd(&s_acc[(idx - it.e0) * F + f], w * g[f]);
+      for (int f = 0; f < F; ++f) add(idx - it.e0, f, w, g[f]);
     }
   }
   __syncthreads();
+}
+
+template <int F>
+__global__ void __launch_bounds__(256) grid_backward_lds_kernel(const GridDevice grid, const LdsBwdItem* __restrict__ items, const float* __restrict__ coords,
+                                                                const half_t* __restrict__ dfeat, uint32_t in_width, typename GridGrad<F>::type* __restrict__ grid_grads)
+{
+  extern __shared__ float s_acc[];   // [e1 - e0][F]
+  const LdsBwdItem it = items[blockIdx.x];
+  const LevelInfo lv = grid.levels[it.level];
+  const uint32_t n_acc = (it.e1 - it.e0) * (uint32_t)F;
+  lds_tile_walk<F>(grid, it, lv, coords, dfeat, in_width, s_acc, n_acc,
+                   [&](uint32_t slot, int f, float w, float g_f) { atomicAdd(&s_acc[slot * F + f], w * g_f); });
   if constexpr (F == 1) {   // fp32 sums into the float image, entry by entry
     float* base = grid_grads + (size_t)lv.offset + it.e0;
     for (uint32_t q = threadIdx.x; q < n_acc; q += blockDim.x) {
@@ -821,38 +813,9 @@ __global__ void __launch_bounds__(256) grid_backward_lds_det_kernel(const GridDe
   const LdsBwdItem it = items[blockIdx.x];
   const LevelInfo lv = grid.levels[it.level];
   const uint32_t n_acc = (it.e1 - it.e0) * (uint32_t)F;
-  for (uint32_t q = threadIdx.x; q < n_acc; q += blockDim.x) s_acc64[q] = 0ull;
-  __syncthreads();
-  const bool nearest = grid.interpolation == 2u;
-  const uint32_t res2 = lv.resolution * lv.resolution;
-  for (uint32_t i = it.s0 + threadIdx.x; i < it.s1; i += blockDim.x) {
-    const float cx = coords[3 * (size_t)i], cy = coords[3 * (size_t)i + 1], cz = coords[3 * (size_t)i + 2];
-    {   // (the early drop of grid_backward_lds_kernel)
-      const uint32_t gx = (uint32_t)(int32_t)__builtin_floorf(__builtin_fmaf(cx, lv.scale, 0.5f));
-      const uint32_t gy = (uint32_t)(int32_t)__builtin_floorf(__builtin_fmaf(cy, lv.scale, 0.5f));
-      const uint32_t gz = (uint32_t)(int32_t)__builtin_floorf(__builtin_fmaf(cz, lv.scale, 0.5f));
-      const uint64_t lo = (uint64_t)gz * res2, hi = ((uint64_t)gz + 2u) * res2 + lv.resolution;
-      const bool in_domain = gx < lv.resolution && gy < lv.resolution && gz < lv.resolution;
-      if (in_domain && hi < lv.size && (hi < it.e0 || lo >= it.e1)) continue;
-    }
-    float g[F];
-    bool any = false;
-#pragma unroll
-    for (int f = 0; f < F; ++f) { g[f] = (float)dfeat[(size_t)i * in_width + it.level * F + f]; any = any || g[f] != 0.0f; }
-    if (!any) continue;
-    const CornerSetup c = level_setup(lv, grid.interpolation == 1u ? 1u : 0u, cx, cy, cz);
-#pragma unroll
-    for (int corner = 0; corner < 8; ++corner) {
-      if (nearest && corner) break;
-      const uint32_t idx = level_index(lv, c.g[0] + (corner & 1), c.g[1] + ((corner >> 1) & 1), c.g[2] + ((corner >> 2) & 1));
-      if (idx < it.e0 || idx >= it.e1) continue;
-      const float w = nearest ? 1.0f : corner_weight(c, corner);
-#pragma unroll
-      for (int f = 0; f < F; ++f)
-        if (g[f] != 0.0f) atomicAdd(&s_acc64[(idx - it.e0) * F + f], det_term(w * g[f], scale));
-    }
-  }
-  __syncthreads();
+  lds_tile_walk<F>(grid, it, lv, coords, dfeat, in_width, s_acc64, n_acc, [&](uint32_t slot, int f, float w, float g_f) {
+    if (g_f != 0.0f) atomicAdd(&s_acc64[slot * F + f], det_term(w * g_f, scale));
+  });
   unsigned long long* base = image + ((size_t)lv.offset + it.e0) * F;
   for (uint32_t q = threadIdx.x; q < n_acc; q += blockDim.x) {
     const unsigned long long a = s_acc64[q];
@@ -1041,39 +1004,45 @@ struct TrainScratch {  // per-Network extra buffers that do not need to live in 
   }
 };
 
-}  // namespace vnr
-
-#include <map>
-#include <memory>
-#include <mutex>
-#include <set>
-
-namespace vnr {
-
-// once per kernel and process: hipFuncSetAttribute stays off the step's launch path.  Keyed by the function's address (the instances of a
-// kernel template share one signature, so a static flag inside a generic lambda would be shared by all of them); guarded, because two
-// host threads may train two networks; the attribute belongs to the function, not to a device.
-static bool first_use_of_kernel(const void* kernel)
+// A launch with more dynamic LDS than the default limit allows.  The limit is raised once per kernel and process, so that the driver call
+// stays off the step's launch path: keyed by the function's address (the instances of a kernel template share one signature, so a static flag
+// per signature would be shared by all of them), and with the mutex held ACROSS the driver call: two host threads may train two networks, and
+// the second must not launch before the first has set the attribute.  The attribute belongs to the function, not to a device.
+static void raise_dynamic_lds_limit(const void* kernel, int limit)
 {
   static std::mutex m;
   static std::set<const void*> done;
   std::lock_guard<std::mutex> g(m);
-  return done.insert(kernel).second;
+  if (done.count(kernel)) return;
+  VNR_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, limit));
+  done.insert(kernel);
+}
+template <class... Params, class... Args>
+static void launch_with_dynamic_lds(void (*kernel)(Params...), dim3 grid, dim3 block, size_t shmem, int limit, hipStream_t s, Args&&... args)
+{
+  raise_dynamic_lds_limit((const void*)kernel, limit);
+  kernel<<<grid, block, shmem, s>>>(std::forward<Args>(args)...);
 }
 
-static std::map<const Network*, std::unique_ptr<TrainScratch>>& scratch_map()
+// the grid backward's kernels exist for 1 / 2 / 4 / 8 features per level: fn(std::integral_constant<int, F>)
+template <class Fn>
+static void with_features(uint32_t n_features, Fn&& fn)
 {
-  static std::map<const Network*, std::unique_ptr<TrainScratch>> m;
-  return m;
+  switch (n_features) {
+  case 1: fn(std::integral_constant<int, 1>{}); break;
+  case 2: fn(std::integral_constant<int, 2>{}); break;
+  case 4: fn(std::integral_constant<int, 4>{}); break;
+  default: fn(std::integral_constant<int, 8>{}); break;
+  }
 }
-static TrainScratch& scratch_of(const Network* n)
+
+void TrainScratchDeleter::operator()(TrainScratch* p) const { delete p; }
+
+TrainScratch& Network::train_scratch() const   // created by the first training call; lives and dies with the network
 {
-  auto& m = scratch_map();
-  auto it = m.find(n);
-  if (it == m.end()) it = m.emplace(n, std::make_unique<TrainScratch>()).first;
-  return *it->second;
+  if (!train_) train_.reset(new TrainScratch);
+  return *train_;
 }
-void network_release_scratch(const Network* n) { scratch_map().erase(n); }
 
 bool Network::deterministic_default()
 {
@@ -1093,8 +1062,28 @@ void Network::reset_master_from_params(hipStream_t s)
   if (opt_state_.count == n_params_) launch_master_from_f16(params_f16_.ptr, opt_state_.ptr, n_params_, false, s);
 }
 
-// 5. of the training step: dL/dfeatures (ws_dfeat_, written by the MLP backward) -> the grid part of the gradient blob.  A function of its
-// own so that it can be repeated alone on the stored dL/dfeatures (vnrAmdNeuralVolumeRescatterGridGradients: diagnostics).
+// slices of the batch per tile of an LDS level: more where a level has few tiles, so that ~2 blocks per CU exist.  The plan's request count
+// (bench.py prices the roofline from it) and the work items are both built from this one line.
+static uint32_t lds_slices(const GridBackwardPlan& plan, uint32_t tiles) { return std::max(4u, std::min(128u, plan.lds_blocks / tiles)); }
+
+// work items of the LDS scatter of levels [l0, l1): every tile of every level x slices of the batch
+static std::vector<LdsBwdItem> lds_backward_items(const GridDevice& grid, const GridBackwardPlan& plan, uint32_t l0, uint32_t l1, size_t batch)
+{
+  std::vector<LdsBwdItem> items;
+  const uint32_t n = (uint32_t)batch;
+  for (uint32_t l = l0; l < l1; ++l) {
+    const uint32_t size = grid.levels[l].size, tiles = div_round_up(size, plan.tile_entries);
+    const uint32_t slices = lds_slices(plan, tiles);
+    const uint32_t per = (uint32_t)div_round_up(batch, slices);
+    for (uint32_t t = 0; t < tiles; ++t)
+      for (uint32_t sl = 0; sl < slices; ++sl) {
+        const uint32_t s0 = sl * per, s1 = std::min<uint32_t>(n, s0 + per);
+        if (s0 < s1) items.push_back({l, t * plan.tile_entries, std::min(size, (t + 1) * plan.tile_entries), s0, s1});
+      }
+  }
+  return items;
+}
+
 // which levels of the grid backward go through LDS tiles, and what the scatter costs in memory-side atomic requests (network.h)
 GridBackwardPlan Network::grid_backward_plan(size_t batch) const
 {
@@ -1119,43 +1108,41 @@ GridBackwardPlan Network::grid_backward_plan(size_t batch) const
   p.atomic_requests = (uint64_t)batch * 4u * (p.n_levels - p.lds_levels) * std::max(1u, (2u * F * elem + 63u) / 64u);
   for (uint32_t l = 0; l < p.lds_levels; ++l) {
     const uint32_t tiles = div_round_up(grid_.levels[l].size, p.tile_entries);
-    const uint32_t slices = std::max(4u, std::min(128u, p.lds_blocks / tiles));
-    p.flush_requests_at_most += (uint64_t)slices * ((uint64_t)grid_.levels[l].size * F * elem / 64u);
+    p.flush_requests_at_most += (uint64_t)lds_slices(p, tiles) *((uint64_t)grid_.levels[l].size * F * elem / 64u);
   }
   return p;
 }
 
+// 5. of the training step: dL/dfeatures (ws_dfeat_, written by the MLP backward) -> the grid part of the gradient blob.  A function of its
+// own so that it can be repeated alone on the stored dL/dfeatures (vnrAmdNeuralVolumeRescatterGridGradients: diagnostics).
 void Network::scatter_grid_gradients(const float* d_coords, size_t batch, hipStream_t s, GradExchange* exchange, hipStream_t s_lds)
 {
   // s_lds: the stream of the dense levels' LDS scatter; another stream than `s` means the two scatters run side by side (forward_backward
   // forks and joins), and the atomic scatter then takes its persistent form so that it leaves room on the CUs
   if (!s_lds) s_lds = s;
   const bool side_by_side = s_lds != s;
-  TrainScratch& ts = scratch_of(this);
+  TrainScratch& ts = train_scratch();
   const uint32_t n = (uint32_t)batch;
-  // 5. hash-grid backward: levels [l0, l1) per launch (blockIdx.y + l0 = level)
-  // levels [0, lds_levels) go through grid_backward_lds_kernel: dense, and at most 64 LDS tiles (grid_backward_plan)
+  // levels [0, lds_levels) go through the LDS kernels: dense, and at most 64 LDS tiles; the rest through the atomic kernels
   const GridBackwardPlan plan = grid_backward_plan(batch);
-  const uint32_t tile_entries = plan.tile_entries, lds_levels = plan.lds_levels, lds_blocks = plan.lds_blocks;
-  // n_features = 1: the scatter's target is the float image (fold_grid_grads_f32_kernel); the fold of a level range follows its scatter on the
-  // same stream(s), before anybody (optimizer, exchange) reads the blob
-  // Deterministic mode (every F): the target of every form is the int64 image, folded the same way; the exponent of the call is computed
-  // first, on `s`, from all active levels' dL/dfeatures (a side stream's LDS scatter waits for it)
-  const bool det = deterministic_;
+  // The target of every form: the fp16 blob's grid part; for n_features = 1 its float image (fold_grid_grads_f32_kernel); in deterministic
+  // mode (every F) the int64 image, with the exponent of the call computed first, on `s`, from all active levels' dL/dfeatures (a side stream's
+  // LDS scatter waits for it).  The fold of a level range follows its scatter on the same stream(s), before anybody (optimizer, exchange)
+  // reads the blob.
   const half_t* dfeat = (const half_t*)ws_dfeat_.ptr;
+  half_t* gg = (half_t*)grads_.ptr + n_mlp_;
   float* gg32 = nullptr;
-  if (cfg_.n_features == 1 && !det) {
-    const size_t n_grid = grads_alloc() - n_mlp_;
+  unsigned long long* gg64 = nullptr;
+  DetScale* d_det = nullptr;
+  const size_t n_grid = grads_alloc() - n_mlp_;
+  if (cfg_.n_features == 1 && !deterministic_) {
     if (ts.grid_grads_f32.count != n_grid) { ts.grid_grads_f32.resize(n_grid); ts.grid_grads_f32.zero(s); VNR_HIP_CHECK(hipStreamSynchronize(s)); }
     gg32 = ts.grid_grads_f32.ptr;
   }
-  long long* gg64 = nullptr;
-  DetScale* d_det = nullptr;
-  if (det && n_active_levels() > 0) {
-    const size_t n_grid = grads_alloc() - n_mlp_;
+  if (deterministic_ && n_active_levels() > 0) {
     if (ts.grid_grads_i64.count != n_grid) { ts.grid_grads_i64.resize(n_grid); ts.grid_grads_i64.zero(s); VNR_HIP_CHECK(hipStreamSynchronize(s)); }
     ts.det_scale.ensure(1);
-    gg64 = ts.grid_grads_i64.ptr;
+    gg64 = (unsigned long long*)ts.grid_grads_i64.ptr;
     d_det = ts.det_scale.ptr;
     VNR_HIP_CHECK(hipMemsetAsync(d_det, 0, sizeof(DetScale), s));
     const uint64_t segs = (uint64_t)batch * (in_width_ / 8u);
@@ -1172,22 +1159,11 @@ void Network::scatter_grid_gradients(const float* d_coords, size_t batch, hipStr
     if ((!gg32 && !gg64) || l0 >= l1) return;
     const size_t lo = level_range_lo(l0) - n_mlp_, hi = level_range_hi(l1) - n_mlp_;
     const uint32_t blocks = (uint32_t)std::min<size_t>(div_round_up(hi - lo, 256), (size_t)Runtime::get().n_cus * 16);
-    if (gg64) fold_grid_grads_det_kernel<<<blocks, 256, 0, s>>>(gg64, (half_t*)grads_.ptr + n_mlp_, lo, hi, d_det);
-    else fold_grid_grads_f32_kernel<<<blocks, 256, 0, s>>>(gg32, (half_t*)grads_.ptr + n_mlp_, lo, hi);
+    if (gg64) fold_grid_grads_det_kernel<<<blocks, 256, 0, s>>>((long long*)gg64, gg, lo, hi, d_det);
+    else fold_grid_grads_f32_kernel<<<blocks, 256, 0, s>>>(gg32, gg, lo, hi);
   };
-  auto grid_backward_lds = [&](uint32_t l0, uint32_t l1) {
-    // work items: every tile of every level x slices of the batch; more slices where a level has few tiles, so that ~2 blocks per CU exist
-    std::vector<LdsBwdItem> items;
-    for (uint32_t l = l0; l < l1; ++l) {
-      const uint32_t size = grid_.levels[l].size, tiles = div_round_up(size, tile_entries);
-      const uint32_t slices = std::max(4u, std::min(128u, lds_blocks / tiles));
-      const uint32_t per = (uint32_t)div_round_up(batch, slices);
-      for (uint32_t t = 0; t < tiles; ++t)
-        for (uint32_t sl = 0; sl < slices; ++sl) {
-          const uint32_t s0 = sl * per, s1 = std::min<uint32_t>(n, s0 + per);
-          if (s0 < s1) items.push_back({l, t * tile_entries, std::min(size, (t + 1) * tile_entries), s0, s1});
-        }
-    }
+  auto lds = [&](uint32_t l0, uint32_t l1) {   // dense levels [l0, l1) through LDS tiles, on s_lds
+    const std::vector<LdsBwdItem> items = lds_backward_items(grid_, plan, l0, l1, batch);
     if (items.empty()) return;
     // (cached on the device while the list is the same: it depends on the level sizes, n_features, the tile size, the batch and the level range,
     // so the bytes themselves are the key: a re-configured model must not reuse the old model's tile and slice ranges)
@@ -1198,80 +1174,37 @@ void Network::scatter_grid_gradients(const float* d_coords, size_t batch, hipStr
       VNR_HIP_CHECK(hipStreamSynchronize(s_lds));   // pageable source
       ts.lds_items_host.assign((const uint8_t*)items.data(), (const uint8_t*)items.data() + item_bytes);
     }
-    if (gg64) {
-      const size_t shmem = (size_t)tile_entries * cfg_.n_features * sizeof(long long);
-      auto launch_det = [&](auto kernel) {
-        if (first_use_of_kernel((const void*)kernel)) VNR_HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        kernel<<<(uint32_t)items.size(), 256, shmem, s_lds>>>(grid_, (const LdsBwdItem*)ts.lds_items.ptr, d_coords, dfeat, in_width_, (unsigned long long*)gg64, d_det);
-      };
-      switch (cfg_.n_features) {
-      case 1: launch_det(grid_backward_lds_det_kernel<1>); break;
-      case 2: launch_det(grid_backward_lds_det_kernel<2>); break;
-      case 4: launch_det(grid_backward_lds_det_kernel<4>); break;
-      default: launch_det(grid_backward_lds_det_kernel<8>); break;
-      }
-      return;
-    }
-    const size_t shmem = (size_t)tile_entries * cfg_.n_features * sizeof(float);
-    half_t* gg = (half_t*)grads_.ptr + n_mlp_;
-    auto launch = [&](auto kernel, auto* out) {
-      if (first_use_of_kernel((const void*)kernel)) VNR_HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      kernel<<<(uint32_t)items.size(), 256, shmem, s_lds>>>(grid_, (const LdsBwdItem*)ts.lds_items.ptr, d_coords, (const half_t*)ws_dfeat_.ptr, in_width_, out);
-    };
-    switch (cfg_.n_features) {
-    case 1: launch(grid_backward_lds_kernel<1>, gg32); break;
-    case 2: launch(grid_backward_lds_kernel<2>, gg); break;
-    case 4: launch(grid_backward_lds_kernel<4>, gg); break;
-    default: launch(grid_backward_lds_kernel<8>, gg); break;
-    }
+    const LdsBwdItem* d_items = (const LdsBwdItem*)ts.lds_items.ptr;
+    const uint32_t blocks = (uint32_t)items.size();
+    const size_t shmem = (size_t)plan.tile_entries * cfg_.n_features * (gg64 ? sizeof(long long) : sizeof(float));
+    with_features(cfg_.n_features, [&](auto f) {
+      constexpr int F = decltype(f)::value;
+      typename GridGrad<F>::type* out;
+      if constexpr (F == 1) out = gg32; else out = gg;
+      if (gg64) launch_with_dynamic_lds(grid_backward_lds_det_kernel<F>, blocks, 256, shmem, 160 * 1024, s_lds, grid_, d_items, d_coords, dfeat, in_width_, gg64, d_det);
+      else launch_with_dynamic_lds(grid_backward_lds_kernel<F>, blocks, 256, shmem, 160 * 1024, s_lds, grid_, d_items, d_coords, dfeat, in_width_, out);
+    });
+  };
+  auto atomic = [&](uint32_t l0, uint32_t l1) {   // levels [l0, l1) with global atomics, on s: a launch's blockIdx.y + l0 = level
+    // lanes per sample: (x bit, feature) in deterministic mode, (x bit, feature pair) in production; persistent form: a few blocks per CU walk them
+    const uint32_t lanes = 2u * (gg64 ? cfg_.n_features : std::max(1u, cfg_.n_features / 2u));
+    const dim3 g(div_round_up((uint64_t)batch * lanes, 256), l1 - l0);
+    constexpr uint32_t kBlocksPerCu = 2;   // (swept 2 / 3 / 4 / 6 / 8, profiles/r05_train_overlap_ab.txt)
+    const uint32_t blocks = std::min<uint32_t>(g.x * g.y, (uint32_t)Runtime::get().n_cus * kBlocksPerCu);
+    with_features(cfg_.n_features, [&](auto f) {
+      constexpr int F = decltype(f)::value;
+      typename GridGrad<F>::type* out;
+      if constexpr (F == 1) out = gg32; else out = gg;
+      if (gg64 && side_by_side) grid_backward_det_persistent_kernel<F><<<blocks, 256, 0, s>>>(grid_, d_coords, dfeat, n, in_width_, gg64, l0, l1 - l0, d_det);
+      else if (gg64) grid_backward_det_kernel<F><<<g, 256, 0, s>>>(grid_, d_coords, dfeat, n, in_width_, gg64, l0, d_det);
+      else if (side_by_side) grid_backward_persistent_kernel<F><<<blocks, 256, 0, s>>>(grid_, d_coords, dfeat, n, in_width_, out, l0, l1 - l0);
+      else grid_backward_kernel<F><<<g, 256, 0, s>>>(grid_, d_coords, dfeat, n, in_width_, out, l0);
+    });
   };
   auto grid_backward = [&](uint32_t l0, uint32_t l1) {
-    if (l0 < lds_levels) {
-      grid_backward_lds(l0, std::min(l1, lds_levels));
-      l0 = std::min(l1, lds_levels);
-      if (l0 >= l1) return;
-    }
-    constexpr uint32_t kBlocksPerCu = 2;   // persistent form (swept 2 / 3 / 4 / 6 / 8, profiles/r05_train_overlap_ab.txt)
-    if (gg64) {   // one lane per (sample, x bit, feature)
-      unsigned long long* img = (unsigned long long*)gg64;
-      const dim3 gd(div_round_up((uint64_t)batch * 2u * cfg_.n_features, 256), l1 - l0);
-      if (side_by_side) {
-        const uint32_t blocks = std::min<uint32_t>(gd.x * gd.y, (uint32_t)Runtime::get().n_cus * kBlocksPerCu);
-        switch (cfg_.n_features) {
-        case 1: grid_backward_det_persistent_kernel<1><<<blocks, 256, 0, s>>>(grid_, d_coords, dfeat, n, in_width_, img, l0, l1 - l0, d_det); break;
-        case 2: grid_backward_det_persistent_kernel<2><<<blocks, 256, 0, s>>>(grid_, d_coords, dfeat, n, in_width_, img, l0, l1 - l0, d_det); break;
-        case 4: grid_backward_det_persistent_kernel<4><<<blocks, 256, 0, s>>>(grid_, d_coords, dfeat, n, in_width_, img, l0, l1 - l0, d_det); break;
-        default: grid_backward_det_persistent_kernel<8><<<blocks, 256, 0, s>>>(grid_, d_coords, dfeat, n, in_width_, img, l0, l1 - l0, d_det); break;
-        }
-        return;
-      }
-      switch (cfg_.n_features) {
-      case 1: grid_backward_det_kernel<1><<<gd, 256, 0, s>>>(grid_, d_coords, dfeat, n, in_width_, img, l0, d_det); break;
-      case 2: grid_backward_det_kernel<2><<<gd, 256, 0, s>>>(grid_, d_coords, dfeat, n, in_width_, img, l0, d_det); break;
-      case 4: grid_backward_det_kernel<4><<<gd, 256, 0, s>>>(grid_, d_coords, dfeat, n, in_width_, img, l0, d_det); break;
-      default: grid_backward_det_kernel<8><<<gd, 256, 0, s>>>(grid_, d_coords, dfeat, n, in_width_, img, l0, d_det); break;
-      }
-      return;
-    }
-    const uint32_t pairs = cfg_.n_features >= 2 ? cfg_.n_features / 2 : 1u;
-    const dim3 g(div_round_up((uint64_t)batch * pairs * 2, 256), l1 - l0);  // one lane per (sample, x bit, feature pair)
-    half_t* gg = (half_t*)grads_.ptr + n_mlp_;
-    if (side_by_side) {   // a few blocks per CU walk the same lanes
-      const uint32_t blocks = std::min<uint32_t>(g.x * g.y, (uint32_t)Runtime::get().n_cus * kBlocksPerCu);
-      switch (cfg_.n_features) {
-      case 1: grid_backward_persistent_kernel<1><<<blocks, 256, 0, s>>>(grid_, d_coords, (const half_t*)ws_dfeat_.ptr, n, in_width_, gg32, l0, l1 - l0); break;
-      case 2: grid_backward_persistent_kernel<2><<<blocks, 256, 0, s>>>(grid_, d_coords, (const half_t*)ws_dfeat_.ptr, n, in_width_, gg, l0, l1 - l0); break;
-      case 4: grid_backward_persistent_kernel<4><<<blocks, 256, 0, s>>>(grid_, d_coords, (const half_t*)ws_dfeat_.ptr, n, in_width_, gg, l0, l1 - l0); break;
-      default: grid_backward_persistent_kernel<8><<<blocks, 256, 0, s>>>(grid_, d_coords, (const half_t*)ws_dfeat_.ptr, n, in_width_, gg, l0, l1 - l0); break;
-      }
-      return;
-    }
-    switch (cfg_.n_features) {
-    case 1: grid_backward_kernel<1><<<g, 256, 0, s>>>(grid_, d_coords, (const half_t*)ws_dfeat_.ptr, n, in_width_, gg32, l0); break;
-    case 2: grid_backward_kernel<2><<<g, 256, 0, s>>>(grid_, d_coords, (const half_t*)ws_dfeat_.ptr, n, in_width_, gg, l0); break;
-    case 4: grid_backward_kernel<4><<<g, 256, 0, s>>>(grid_, d_coords, (const half_t*)ws_dfeat_.ptr, n, in_width_, gg, l0); break;
-    default: grid_backward_kernel<8><<<g, 256, 0, s>>>(grid_, d_coords, (const half_t*)ws_dfeat_.ptr, n, in_width_, gg, l0); break;
-    }
+    const uint32_t split = std::max(l0, std::min(l1, plan.lds_levels));
+    if (l0 < split) lds(l0, split);
+    if (split < l1) atomic(split, l1);
   };
   if (!exchange) {
     // diagnostics builds (-DVNR_DIAG; tools/train_probe.py): VNR_AMD_GRID_BWD_LEVELS="l0,l1" scatters levels [l0, l1) only, to price a level
@@ -1312,7 +1245,7 @@ void Network::forward_backward(const float* d_coords, const float* d_targets, si
   if (!valid()) throw std::runtime_error("network is not configured");
   if (batch == 0) return;
   // every model the reference's dispatch builds runs on the MFMA kernels (tcnn_network.h:163-252 builds whatever the model JSON asks for)
-  TrainScratch& ts = scratch_of(this);
+  TrainScratch& ts = train_scratch();
   const uint32_t nh = n_hidden_matmuls();
   const uint32_t n = (uint32_t)batch;
   const uint32_t Wn = cfg_.n_neurons;
@@ -1365,12 +1298,7 @@ void Network::forward_backward(const float* d_coords, const float* d_targets, si
     const uint32_t fit = (uint32_t)std::max<size_t>(1, std::min<size_t>(4, kLdsBytes / shmem));
     const uint32_t blocks = std::min<uint32_t>(div_round_up(div_round_up(batch, 64), 4), (uint32_t)Runtime::get().n_cus * fit);
     const int mt = (int)((in_width_ + 31) / 32);
-    auto launch = [&](auto kernel) {
-      // once per kernel: no driver call on the step's launch path.  (Keyed by the function's address: the instances share one signature,
-      // so a static flag inside this generic lambda would be shared by all of them.)
-      if (first_use_of_kernel((const void*)kernel)) VNR_HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes));
-      kernel<<<blocks, 256, shmem, s>>>(ba);
-    };
+    auto launch = [&](auto kernel) { launch_with_dynamic_lds(kernel, blocks, 256, shmem, (int)kLdsBytes, s, ba); };
     const bool gen = cfg_.activation > 1u || bwd_global;
 #define VNR_BWD_G(w, g) do { if (mt == 1) launch(mlp_backward_kernel<w, 1, g>); else if (mt == 2) launch(mlp_backward_kernel<w, 2, g>); \
                              else if (mt == 3) launch(mlp_backward_kernel<w, 3, g>); else launch(mlp_backward_kernel<w, 4, g>); } while (0)
@@ -1501,14 +1429,14 @@ const void* Network::training_buffer(int which, size_t* bytes) const
   case 2: *bytes = ws_features_.bytes(); return ws_features_.ptr;
   case 3: *bytes = ws_acts_.bytes(); return ws_acts_.ptr;
   case 4: {   // the deterministic mode's int64 image of the grid part (zero between steps; absent before the first deterministic step)
-    const TrainScratch& ts = scratch_of(this);
+    const TrainScratch& ts = train_scratch();
     *bytes = ts.grid_grads_i64.bytes();
     return ts.grid_grads_i64.ptr;
   }
   // the MLP backward's own intermediates (tests/test_gpu_mlp_stages.py holds every stage of the step to the inputs it read)
-  case 5: { const TrainScratch& ts = scratch_of(this); *bytes = ts.d_all.bytes(); return ts.d_all.ptr; }
-  case 6: { const TrainScratch& ts = scratch_of(this); *bytes = ts.dy.bytes(); return ts.dy.ptr; }
-  case 7: { const TrainScratch& ts = scratch_of(this); *bytes = ts.y.bytes(); return ts.y.ptr; }
+  case 5: { const TrainScratch& ts = train_scratch(); *bytes = ts.d_all.bytes(); return ts.d_all.ptr; }
+  case 6: { const TrainScratch& ts = train_scratch(); *bytes = ts.dy.bytes(); return ts.dy.ptr; }
+  case 7: { const TrainScratch& ts = train_scratch(); *bytes = ts.y.bytes(); return ts.y.ptr; }
   default: throw std::runtime_error("training_buffer: 0 gradients, 1 dL/dfeatures, 2 features, 3 activations, 4 the deterministic int64 image, "
                                     "5 dL/d(pre-activation) of every hidden layer, 6 dL/dy, 7 the training forward's output");
   }
@@ -1544,7 +1472,7 @@ void Network::gradient_distance(const uint16_t* d_ref, double out[4], hipStream_
 {
   if (grads_.count != grads_alloc()) throw std::runtime_error("gradient_distance: no gradient yet");
   constexpr uint32_t kBlocks = 256;
-  DeviceBuffer<double>& part = scratch_of(this).distance_partials;   // (per network, released with its scratch: nothing static that outlives the HIP runtime)
+  DeviceBuffer<double>& part = train_scratch().distance_partials;   // (per network, released with its scratch: nothing static that outlives the HIP runtime)
   part.ensure(4 * kBlocks);
   grad_distance_kernel<<<kBlocks, 256, 0, s>>>((const half_t*)grads_.ptr, (const half_t*)d_ref, 0, n_mlp_, part.ptr);
   grad_distance_kernel<<<kBlocks, 256, 0, s>>>((const half_t*)grads_.ptr, (const half_t*)d_ref, n_mlp_, n_params_, part.ptr + 2 * kBlocks);
@@ -1582,7 +1510,7 @@ void Network::optimizer_finish_step(hipStream_t s)
 
 double Network::training_loss(hipStream_t s)
 {
-  TrainScratch& ts = scratch_of(this);
+  TrainScratch& ts = train_scratch();
   if (ts.loss_blocks == 0) return 0.0;
   std::vector<float> h(ts.loss_blocks);
   ws_loss_.download(h.data(), ts.loss_blocks, s);

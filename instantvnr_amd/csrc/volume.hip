@@ -639,8 +639,6 @@ static void reduce_errors(const float* pred, const float* ref, size_t n, bool l2
 }
 
 // ================================================================================================ NeuralVolume
-void network_release_scratch(const Network* n);
-
 
 // value ranges are stored as (min - 1, max + 1) with 0 = "nothing seen yet" (macrocell.cu:35-39, 213-219): min - 1 <= 0 and
 // max + 1 >= 1, so the element-wise MIN over ranks of .x and MAX of .y merge the ranks' macrocells, untouched cells included
@@ -744,7 +742,7 @@ NeuralVolume::NeuralVolume()
   stream = Runtime::get().stream;
 }
 
-NeuralVolume::~NeuralVolume() { network_release_scratch(&net_); }
+NeuralVolume::~NeuralVolume() = default;   // (the network owns its training scratch)
 
 void NeuralVolume::set_transfer_function(const TransferFunctionData& t, hipStream_t s)
 {

@@ -157,6 +157,69 @@ def test_lds_tiles_of_a_65536_sample_batch_give_the_exact_sum(oracle):
     check_exact(g[n_mlp:], S, A, K, exponent(dfeat, 6 * 2), "lds 65536")
 
 
+# ------------------------------------------------------------------------------------------------ every form of the scatter, every F
+# One model per F on which a step takes all three kinds of level: dense levels through LDS tiles, a dense level with more than 64 tiles
+# (global atomics on a dense index) and a hashed level; 8 192 samples, the smallest batch at which VNR_AMD_TRAIN_OVERLAP=1 takes the
+# persistent forms.  Production and deterministic mode, one stream and side by side: the six kernel forms of that F in one case.
+ALL_FORMS_MODELS = {1: dict(L=6, F=1, log2T=19, base=5), 2: dict(L=6, F=2, log2T=18, base=4), 4: dict(L=5, F=4, log2T=17, base=6),
+                    8: dict(L=5, F=8, log2T=16, base=5)}
+ALL_FORMS_BATCH = 8192
+
+
+def _faces_and_just_outside(coords):
+    """the domain's faces and corners, and values just outside [0, 1], in the first rows (the LDS kernels' early drop must keep them)"""
+    eps = np.float32(2.0 ** -20)
+    lo, hi = np.nextafter(np.float32(0), np.float32(-1)), np.nextafter(np.float32(1), np.float32(2))
+    special = [(0, 0, 0), (1, 1, 1), (1, 0, 0.5), (0.5, 1, 0), (0, 0.25, 1), (lo, lo, lo), (hi, hi, hi), (-eps, 0.5, 0.5), (0.5, 1 + eps, 0.5),
+               (0.5, 0.5, -1e-3), (0.3, 0.7, 1.001), (1.001, -1e-3, 1), (0, hi, lo), (1 - eps, 1 - eps, 1 - eps)]
+    coords[:len(special)] = np.array(special, np.float32)
+    return coords
+
+
+@pytest.mark.parametrize("interp", ["Linear", "Smoothstep", "Nearest"])
+@pytest.mark.parametrize("F", [1, 2, 4, 8])
+def test_every_form_of_the_scatter_gives_the_exact_sum_or_stays_within_the_production_bound(oracle, monkeypatch, F, interp):
+    kw = ALL_FORMS_MODELS[F]
+    n = ALL_FORMS_BATCH
+    vol, ocfg, info, n_mlp, params = make_model(oracle, seed=40 + F, interp=interp, **kw)
+    levels = api.neural_level_table(vol)
+    plans = {}
+    for det in (False, True):                                 # the model is chosen by what the library plans for it, in either mode
+        api.neural_set_deterministic_training(vol, det)
+        plan = plans[det] = api.neural_grid_backward_plan(vol, n)
+        assert plan["n_levels"] == kw["L"] and 1 <= plan["lds_levels"] < plan["n_levels"], plan
+        assert levels[plan["lds_levels"]]["kind"] == 0, ("a dense level beyond the LDS levels", plan, levels)
+        assert any(lv["kind"] == 1 for lv in levels[plan["lds_levels"]:]), ("a hashed level", levels)
+    coords, targets = batch(n, 50 + F)
+    coords = _faces_and_just_outside(coords)
+
+    def run(det, overlap):
+        api.neural_set_deterministic_training(vol, det)
+        monkeypatch.setenv("VNR_AMD_TRAIN_OVERLAP", "1" if overlap else "0")
+        api.neural_forward_backward(vol, coords, targets)
+        g = blob(vol)[n_mlp:info["n_params"]].copy()
+        dfeat = training_buffer(vol, 1, np.float16).reshape(n, info["padded_width"]).copy()
+        api.neural_train_end(vol, grad_scale=0.0)            # clears the blob for the next run ...
+        api.neural_set_params_fp16(vol, params)                # ... and the same parameters again
+        return g, dfeat
+
+    det_one, dfeat = run(True, False)
+    S, A, K, lay = exact_scatter(oracle, ocfg, dfeat, coords)
+    e = exponent(dfeat, kw["L"] * F)
+    assert e is not None and np.abs(S).max() > 0
+    check_exact(det_one, S, A, K, e, ("deterministic, one stream", F, interp))
+    det_side, dfeat2 = run(True, True)
+    assert np.array_equal(dfeat2.view(np.uint16), dfeat.view(np.uint16))
+    assert np.array_equal(det_side.view(np.uint16), det_one.view(np.uint16)), ("side by side", F, interp, int((det_side != det_one).sum()))
+    assert not training_buffer(vol, 4, np.int64).any(), "the int64 image is zero after the fold"
+    bound = production_bound(S, A, K, F, _lds_slices_per_element(vol, plans[False], lay, F, S.size))
+    for overlap in (False, True):
+        prod, dfeat3 = run(False, overlap)
+        assert np.array_equal(dfeat3.view(np.uint16), dfeat.view(np.uint16))
+        err = np.abs(prod.astype(np.float64) - S)
+        assert (err <= bound).all(), ("production", "side by side" if overlap else "one stream", F, interp, np.nonzero(err > bound)[0][:8].tolist())
+
+
 # ------------------------------------------------------------------------------------------------ bit-reproducible training
 def _train_run(cfg, params, steps, overlap, per_step_params):
     os.environ["VNR_AMD_TRAIN_OVERLAP"] = "1" if overlap else "0"

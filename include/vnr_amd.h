@@ -590,7 +590,7 @@ vnrAmdCorrection vnrAmdCreateCorrectionFromCodedBytes(const void* bytes, size_t 
 int  vnrAmdCorrectionSerializeCodedToDevice(vnrAmdCorrection, void* d_bytes, size_t capacity, size_t* size, void* stream);
 /* hash-grid encode only (tcnn_impl_decoder.cu:177-230, column = level*F + f): fp16 [n][padded_width] */
 int    vnrAmdNeuralVolumeEncode(vnrAmdVolume, size_t n, const float* d_coords, uint16_t* d_features, void* stream);
-/* AMD extension: state of the brick image, the de-hashed inference copy of the hashed levels (csrc/network.h).  It is built
+/* AMD extension: state of the brick image, the de-hashed inference copy of the hashed levels (csrc/grid_levels.h, csrc/brick_cache.h).  It is built
  * once the parameters have been left unchanged for VNR_AMD_BRICK_AFTER (24) inference launches and dropped when they change;
  * VNR_AMD_BRICK=0 disables it, =1 builds it at the first launch; its size is bounded (SetBrickImageBudget below).  Results do not depend on it. */
 int    vnrAmdNeuralVolumeBrickImageInfo(vnrAmdVolume, int* in_use, size_t* bytes, float* build_ms);

@@ -851,10 +851,10 @@ int vnrAmdNeuralVolumeEncode(vnrAmdVolume v, size_t n, const float* d_coords, ui
 int vnrAmdNeuralVolumeBrickImageInfo(vnrAmdVolume v, int* in_use, size_t* bytes, float* build_ms)
 {
   return guarded([&]() {
-    Network& n = as_neural(v)->network();
-    if (in_use) *in_use = n.brick_image_in_use() ? 1 : 0;
-    if (bytes) *bytes = n.brick_image_bytes();
-    if (build_ms) *build_ms = n.brick_build_ms();
+    const BrickCache& c = as_neural(v)->network().brick_cache();
+    if (in_use) *in_use = c.in_use() ? 1 : 0;
+    if (bytes) *bytes = c.bytes();
+    if (build_ms) *build_ms = c.build_ms();
   });
 }
 int vnrAmdNeuralVolumeGetModelKind(vnrAmdVolume v, int* activation, int* output_activation, int* grid_type, int* interpolation, int* mfma_inference,
@@ -1261,22 +1261,22 @@ int vnrAmdNeuralVolumeTrainDataParallel(vnrAmdVolume v, int steps, int fast_mode
 {
   return guarded([&]() { as_neural(v)->train_data_parallel((size_t)std::max(steps, 0), fast_mode != 0); });
 }
-int vnrAmdNeuralVolumeSetBrickImageMode(vnrAmdVolume v, int mode) { return guarded([&]() { as_neural(v)->network().set_brick_mode(mode); }); }
-int vnrAmdNeuralVolumeSetBrickImageBudget(vnrAmdVolume v, size_t bytes) { return guarded([&]() { as_neural(v)->network().set_brick_budget(bytes); }); }
+int vnrAmdNeuralVolumeSetBrickImageMode(vnrAmdVolume v, int mode) { return guarded([&]() { as_neural(v)->network().brick_cache().set_mode(mode); }); }
+int vnrAmdNeuralVolumeSetBrickImageBudget(vnrAmdVolume v, size_t bytes) { return guarded([&]() { as_neural(v)->network().brick_cache().set_budget(bytes); }); }
 unsigned vnrAmdNeuralVolumeBrickImageLevels(vnrAmdVolume v)
 {
   unsigned m = 0;
-  guarded([&]() { m = as_neural(v)->network().brick_levels_mask(); });
+  guarded([&]() { m = as_neural(v)->network().brick_cache().levels_mask(); });
   return m;
 }
 int vnrAmdNeuralVolumeBrickImagePolicy(vnrAmdVolume v, uint64_t* builds, unsigned* launches_before_next_build, int* tier, uint64_t* small_builds)
 {
   return guarded([&]() {
-    Network& n = as_neural(v)->network();
-    if (builds) *builds = n.brick_builds();
-    if (launches_before_next_build) *launches_before_next_build = n.brick_after_now();
-    if (tier) *tier = n.brick_tier();
-    if (small_builds) *small_builds = n.brick_small_builds();
+    const BrickCache& c = as_neural(v)->network().brick_cache();
+    if (builds) *builds = c.policy().builds;
+    if (launches_before_next_build) *launches_before_next_build = c.after_now();
+    if (tier) *tier = c.policy().tier;
+    if (small_builds) *small_builds = c.policy().small_builds;
   });
 }
 int vnrAmdNeuralVolumeGridBackwardPlan(vnrAmdVolume v, uint64_t batch, uint32_t out_u32[4], uint64_t out_u64[2])

@@ -314,7 +314,7 @@ __device__ __forceinline__ bool gather_corners_brick(const LevelInfo& lv, const 
     const bool bad = (c.g[0] >= res) | (c.g[1] >= res) | (c.g[2] >= res);
     if (__builtin_amdgcn_ballot_w64(bad) != 0ull) return false;
     const uint32_t nbx = lv.pad1, nby = (res >> 1) + 1u;   // scalar
-    const uint32_t bx = (c.g[0] * 9363u) >> 16;            // x / 7, exact for x < 13 107 (build_brick_image bricks no finer level)
+    const uint32_t bx = (c.g[0] * 9363u) >> 16;            // x / 7, exact for x < 13 107 (plan_brick_image bricks no finer level)
     const uint32_t wx = c.g[0] - 7u * bx, wy = c.g[1] & 1u, wz = c.g[2] & 1u;
     const uint32_t brick = __umul24(__umul24(c.g[2] >> 1, nby) + (c.g[1] >> 1), nbx) + bx;
     const uint32_t e0 = brick * 32u + ((wz << 4) | (wy << 3) | wx);

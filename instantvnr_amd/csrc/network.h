@@ -10,40 +10,15 @@
 #include <utility>
 #include <vector>
 
+#include "brick_cache.h"
 #include "common.h"
+#include "grid_levels.h"
 #include "json.h"
 
 namespace vnr {
 
-constexpr int kMaxLevels = 32;
 constexpr size_t kLdsBytes = 160 * 1024;   // LDS of a CU: what a weight image may take
 constexpr int kLossScale = 128;   // tcnn default loss scale for fp16 (EXTERNAL)
-
-struct LevelInfo {
-  float scale;
-  uint32_t resolution;
-  uint32_t res2;    // resolution^2 (dense index stride of z)
-  uint32_t size;    // entries in this level
-  uint32_t offset;  // first entry of this level (entries, x F for elements)
-  uint32_t hashed;  // 0: dense index, 1: prime-XOR hash (size is a power of two), 2 / 3 / 4: Tiled grid, index over 1 / 2 / 3 dimensions modulo size
-  uint32_t brick;   // 0: read the parameter blob; else 1 + first 128-byte line of this level in the brick image (below)
-  uint32_t pad1;    // bricked levels with F = 2: bricks per row of the image (resolution / 7 + 1); else 0.  32 bytes: one s_load_dwordx8 per level
-};
-
-// Brick image (inference only): a level whose table is hashed is ALSO kept de-hashed, as a dense array over the level's
-// (res + 1)^3 grid points stored in bricks of one 128-byte line: 4x4x4 entries for F = 1, 4x2x2 for F = 4, 2x2x2 for F = 8, and
-// for F = 2 8x2x2 entries of which the 8th column repeats the +x neighbour's first (grid_device.h: a cell's x-pairs never straddle).  The values are copies (image[x, y, z] = table[hash(x, y, z)]), so results are bit-identical; what changes
-// is which lines a wave touches: the 8 corners of a cell fall into ~2.3 lines instead of 4-8 and neighbouring samples share
-// them, where the hash scatters every (y, z) row to an unrelated line (measured on the bench frame's sample queue: 917 -> 385
-// fetched bytes per sample inside a 64-sample wave).  The price is memory, 8.8 GB instead of 140 MB for the bench model,
-// which is what 288 GB of HBM are for, and a rebuild (a few ms) after the parameters change, so the image is only built once
-// the parameters have been left alone for a while (Network::brick_policy).
-template <int F> struct BrickShape;
-template <> struct BrickShape<1> { static constexpr uint32_t lx = 2, ly = 2, lz = 2; };
-template <> struct BrickShape<2> { static constexpr uint32_t lx = 2, ly = 2, lz = 1; };   // (superseded for the image itself: F = 2 uses 8 x 2 x 2 bricks
-                                                                                          // with a repeated column, grid_device.h gather_corners_brick; kept for the sizing code's defaults)
-template <> struct BrickShape<4> { static constexpr uint32_t lx = 2, ly = 1, lz = 1; };
-template <> struct BrickShape<8> { static constexpr uint32_t lx = 1, ly = 1, lz = 1; };
 
 struct GridDevice {
   LevelInfo levels[kMaxLevels];
@@ -224,36 +199,16 @@ public:
   void release_temporary();
   static void release_temporary_of_all();
 
-  // brick image policy: built on stream `s` once `brick_after` inference launches have seen unchanged parameters
-  // (VNR_AMD_BRICK_AFTER, default 24 = two frames of the streaming renderer; VNR_AMD_BRICK=0 disables, =1 builds at the first
-  // launch), within VNR_AMD_BRICK_MAX_GB (default 32) and a quarter of the free device memory
-  // Levels finer than `cap` grid points per axis are left hashed: the image pays off where neighbouring samples share cells,
-  // i.e. up to about the resolution of the volume the network represents (NeuralVolume passes twice its largest dimension).
-  // A 128^3 volume with tcnn's default per_level_scale 2 has levels up to 2048^3, whose image would be 137 GB and useless.
-  void set_brick_resolution_cap(uint32_t cap) { brick_res_cap_ = cap; }
-  // -1: the environment's policy (VNR_AMD_BRICK, default automatic), 0: never (drops an existing image), 1: build at the next launch
-  void set_brick_mode(int mode);
-  // budget of the image in bytes (0: the default policy, network_host.hip build_brick_image); drops an existing image, which is rebuilt
-  // within the new budget by the next launches.  Levels are taken finest first while they fit.
-  void set_brick_budget(size_t bytes);
+  // the inference cache (brick_cache.h): mode, budget and resolution cap are set on it, and its state is read from it
+  BrickCache& brick_cache() const { return brick_; }
   GridBackwardPlan grid_backward_plan(size_t batch) const;
-  uint32_t brick_levels_mask() const { return brick_levels_mask_; }   // bit l: level l is read from the image
-  bool brick_image_in_use() const { return brick_valid_; }
-  size_t brick_image_bytes() const { return brick_image_.bytes(); }
-  float brick_build_ms() const { return brick_build_ms_; }
-  uint64_t brick_builds() const { return brick_builds_; }              // how many times the (full) image has been built
-  uint64_t brick_small_builds() const { return brick_small_builds_; }  // ... and its small tier
-  int brick_tier() const { return brick_valid_ ? brick_tier_ : 0; }    // 0 none, 1 small, 2 full
-  uint32_t brick_after_now() const;                                    // launches with unchanged parameters the next build waits for
 
 private:
   void build_layout();
   void initialize_params(uint64_t seed, hipStream_t s);
   void refresh_inference_weights(hipStream_t s);
   FusedMlp fused_mlp() const;
-  const LevelInfo* inference_levels(hipStream_t s, const uint8_t** image, size_t n_max) const;  // decides / builds / orders streams
-  void build_brick_image(hipStream_t s, bool small) const;
-  static double brick_small_budget();
+  BrickCache::Source brick_source() const { return {grid_.levels, grid_.n_levels, grid_.n_features, params_f16_.ptr + n_mlp_, levels_dev_.ptr}; }
   TrainScratch& train_scratch() const;   // created on first use
 
   ModelConfig cfg_;
@@ -285,32 +240,7 @@ private:
   hipStream_t side_stream_ = nullptr;
   hipEvent_t ev_fork_ = nullptr, ev_join_ = nullptr;
   uint32_t lds_halves_ = 0, lds_halves_T_ = 0;
-  // brick image (inference cache; mutable: built lazily from const inference calls)
-  mutable DeviceBuffer<uint8_t> brick_image_{MemTag::Network};
-  mutable DeviceBuffer<LevelInfo> levels_brick_dev_{MemTag::Network};
-  mutable bool brick_valid_ = false, brick_refused_ = false;
-  mutable uint32_t brick_stable_calls_ = 0;
-  // An application that trains while it renders (apps/int_dual_volume.cpp:631-672) changes the parameters after every frame.  An image
-  // built between two optimizer steps costs more than it saves (6.5 ms for the C4 model against 0.1 ms saved per launch), and whether the
-  // base threshold is reached inside one frame depends on the frame (ray parts x iterations: 12 launches for the bench frame, 27 for a
-  // three-part share of it).  So the threshold backs off: an image dropped before it served `kBrickPaysAfter` launches doubles it, an
-  // image that lived longer resets it.
-  static constexpr uint32_t kBrickPaysAfter = 64;
-  mutable uint32_t brick_served_calls_ = 0, brick_after_scale_ = 1;
-  mutable uint64_t brick_builds_ = 0;
-  // Two tiers (round 6).  FULL: the policy above.  SMALL: while the parameters keep changing, the first large evaluation launch after a change
-  // (capacity >= kBrickSmallMinLaunch samples: a frame, not a probe) builds the finest-first levels that fit brick_small_budget(), 0.25 ms for
-  // the bench model's 0.7 GB, which the frame's ~12 launches earn back: the reference application's loop 190 -> 200 frames/s.  A small image
-  // never counts towards the backoff above, and it is replaced by the full one once the parameters have been left alone.
-  static constexpr size_t kBrickSmallMinLaunch = (size_t)1 << 20;
-  mutable int brick_tier_ = 0;   // 0 none, 1 small, 2 full
-  mutable bool brick_small_refused_ = false;   // no level fits the small budget
-  mutable uint64_t brick_small_builds_ = 0;
-  mutable float brick_build_ms_ = 0.0f;
-  uint32_t brick_res_cap_ = 0;   // 0: no cap
-  size_t brick_budget_ = 0;      // 0: default policy
-  mutable uint32_t brick_levels_mask_ = 0;
-  int brick_mode_ = -1;
+  mutable BrickCache brick_;   // (mutable: built lazily from const inference calls)
 
 public:
   // Per-kernel time of the training step (HIP events on the training stream, a ring of the last kTrainProfileSteps steps):

@@ -770,7 +770,7 @@ void NeuralVolume::set_network(vec3i dims, const Json& config, SimpleVolume* ref
   net_.configure(config, seed);
   replicas_synced_ = false;   // (a data-parallel run re-synchronises: the clock seed may differ between ranks)
   dp_.reset();
-  net_.set_brick_resolution_cap(2u * (uint32_t)std::max(desc.dims.x, std::max(desc.dims.y, desc.dims.z)));
+  net_.brick_cache().set_resolution_cap(2u * (uint32_t)std::max(desc.dims.x, std::max(desc.dims.y, desc.dims.z)));
   train_x_.resize(batch_size_ * 3);
   train_y_.resize(batch_size_);
   test_y1_.resize(batch_size_);
@@ -790,7 +790,7 @@ void NeuralVolume::set_model(const Json& config)
   net_.configure(config, seed);
   replicas_synced_ = false;
   dp_.reset();
-  net_.set_brick_resolution_cap(2u * (uint32_t)std::max(desc.dims.x, std::max(desc.dims.y, desc.dims.z)));
+  net_.brick_cache().set_resolution_cap(2u * (uint32_t)std::max(desc.dims.x, std::max(desc.dims.y, desc.dims.z)));
 }
 
 void NeuralVolume::train_begin()

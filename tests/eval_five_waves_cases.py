@@ -13,7 +13,7 @@ L, F, LOG2_T, BASE, PLS, NEURONS, HIDDEN = 8, 2, 12, 4, 1.5, 64, 2
 PADDED_WIDTH = 16
 N_MLP = NEURONS * PADDED_WIDTH + (HIDDEN - 1) * NEURONS * NEURONS + 16 * NEURONS   # first, hidden, last (16 padded rows)
 PARAM_SEED, POINT_SEED = 808, 809
-BIG_LAUNCH = 1 << 20   # samples of a launch that counts as a frame for the small tier of the brick image (csrc/network.h kBrickSmallMinLaunch)
+BIG_LAUNCH = 1 << 20   # samples of a launch that counts as a frame for the small tier of the brick image (csrc/brick_policy.h kSmallMinLaunch)
 
 
 def make_volume():

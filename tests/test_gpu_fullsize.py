@@ -158,6 +158,7 @@ def test_the_small_cache_tier_serves_a_train_while_render_loop_bit_for_bit(big_s
         got = api.vnrRendererMapFrame(r).copy()
         st = api.neural_brick_image(nv)
         assert st["tier"] == 1 and st["in_use"], st
+        small_image = st
         check(lib().vnrAmdNeuralVolumeSetBrickImageMode(nv.h, 0))      # the same parameters without any cache
         api.vnrRendererResetAccumulation(r)
         api.vnrRender(r)
@@ -170,8 +171,11 @@ def test_the_small_cache_tier_serves_a_train_while_render_loop_bit_for_bit(big_s
     assert st["launches_before_next_build"] == st0["launches_before_next_build"]        # small images do not move the full tier's backoff
     for _ in range(2 + st["launches_before_next_build"] // 4):
         api.vnrRender(r); api.vnrRendererMapFrame(r)
-    st = api.neural_brick_image(nv)
-    assert st["tier"] == 2 and st["builds"] == st0["builds"] + 1, st
+    small, st = st, api.neural_brick_image(nv)
+    # every bricked level of this model fits the small budget, so the small image these frames began with IS the full one: it is promoted as
+    # it stands, and `builds` counts only images whose build kernels ran (csrc/brick_policy.h)
+    assert st["tier"] == 2 and st["bytes"] == small_image["bytes"] and st["levels"] == small_image["levels"], (st, small_image)
+    assert st["builds"] == st0["builds"] and st["small_builds"] == small["small_builds"] + 1, st
 
 
 def small_frame(scene):

@@ -541,7 +541,7 @@ def test_encoding_shapes_without_a_kernel_instance_are_refused_when_the_model_is
 
 @pytest.mark.parametrize("F,budget,want", [(8, 4_800_000, [2, 3]), (2, 1_450_000, [2, 4])])
 def test_which_levels_the_inference_cache_takes_when_not_all_fit(oracle, F, budget, want):
-    """network_host.hip build_brick_image: big bricks (F <= 2: 32 / 64 entries) take the FINEST hashed levels that fit, small bricks (F >= 4:
+    """brick_policy.cpp plan_brick_image: big bricks (F <= 2: 32 / 64 entries) take the FINEST hashed levels that fit, small bricks (F >= 4:
     2 x 2 x 2 cells for F = 8) the COARSEST (round 6: the reference's example model on a 1024^3 volume spent 17.6 GB on its finest level for
     nothing).  Hashed levels 2..5 of resolution 16 / 32 / 64 / 128; the budget holds level 4 and one small level, or levels 2 and 3.  Bit-exact
     either way."""

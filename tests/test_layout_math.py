@@ -4,7 +4,7 @@ import numpy as np
 
 
 def test_brick_column_division_by_seven_is_exact_for_every_bricked_level():
-    """grid_device.h: bx = (x * 9363) >> 16 replaces x / 7 for the 8 x 2 x 2 bricks with a repeated column; build_brick_image keeps
+    """grid_device.h: bx = (x * 9363) >> 16 replaces x / 7 for the 8 x 2 x 2 bricks with a repeated column; plan_brick_image (csrc/brick_policy.cpp) keeps
     levels of 13 000 grid points per axis or more hashed, so the identity must hold below that (it first fails at x = 13 108)"""
     x = np.arange(0, 13000 + 2, dtype=np.uint64)
     assert np.array_equal((x * 9363) >> 16, x // 7)

@@ -588,6 +588,57 @@ int  vnrAmdCorrectionSerializePackedToDevice(vnrAmdCorrection, void* d_bytes, si
 int  vnrAmdCorrectionSerializeCoded(vnrAmdCorrection, void** bytes, size_t* size);
 vnrAmdCorrection vnrAmdCreateCorrectionFromCodedBytes(const void* bytes, size_t size);
 int  vnrAmdCorrectionSerializeCodedToDevice(vnrAmdCorrection, void* d_bytes, size_t capacity, size_t* size, void* stream);
+/* AMD extension: random access to the corrected field.  A list of voxels or of positions instead of a box: no box around a query is
+ * decoded, and the correction is read in whichever form is resident, at its resident size.  One lane takes one query.
+ *
+ * GatherVoxelsCorrected: d_voxels holds n triples {x, y, z} of int32, grid indices of the volume's own grid, in any order,
+ * duplicates allowed; d_out receives n elements of the correction's value type, dense.  out[j] is bit for bit what
+ * DecodeToDeviceCorrected stores at voxel d_voxels[j], for every value type, kind and resident form.  Only the n listed voxels are
+ * evaluated, at ((float)x + 0.5f) * (1.0f / (float)dims.x) and likewise y and z (the decode's arithmetic), through the decode's
+ * scratch in chunks of VNR_AMD_DECODE_CHUNK samples; the result does not depend on the chunk size.  A voxel's cell, its index in the
+ * cell and its code are those of the apply ("error-bounded round trip", "resident form" above).  A correction without flagged cells
+ * gives the plain typed decode of those voxels and nothing is uploaded for it; the first use of a correction read from bytes uploads
+ * exactly the resident form that is set, as the apply does (PACKED set beforehand never allocates the fixed-width payload).
+ * The whole list is validated on the device before any voxel is evaluated (a ballot per wavefront, an atomic minimum on the list
+ * position): a voxel with a component < 0 or >= dims refuses the call with the lowest such j and its triple named, and nothing has
+ * been written to d_out.
+ *
+ * SampleCorrected: d_coords holds n positions {x, y, z} in [0, 1] as for vnrAmdNeuralVolumeInference, d_values receives n float32 in
+ * the data units of the correction's range.  The field is continuous: the converted network value plus the trilinear blend of the
+ * stored residuals of the eight voxel centres around the position.  Every step is one IEEE operation:
+ *   v = the value vnrAmdNeuralVolumeInference gives at the position;
+ *   d = __fadd_rn(__fmul_rn(v, range_hi - range_lo), range_lo) (the subtraction in float as well), d = v when range_lo > range_hi:
+ *       DecodeToDevice's conversion to FLOAT, NOT rounded to an integer value type;
+ *   per axis, in fp32: t = __fsub_rn(__fmul_rn(p, (float)dim), 0.5f); if !(t >= 0) then t = 0 (a NaN coordinate lands here); if
+ *       t > (float)(dim - 1) then t = (float)(dim - 1); i0 = (int)floorf(t), i1 = min(i0 + 1, dim - 1), w = __fsub_rn(t, (float)i0),
+ *       which is exact;
+ *   the residual of a voxel, a double: 0 in a cell that is not flagged; kind 0 (double)(clamp(q, -qmax, qmax) * s) formed in int64,
+ *       qmax = 2^34 / s + 1; kind 1 __dmul_rn((double)q, s); q is read as the apply reads it, from the cell table and the
+ *       fixed-width payload or from the bit planes;
+ *   lerp(a, b, w) = __dadd_rn(__dmul_rn(a, __dsub_rn(1.0, (double)w)), __dmul_rn(b, (double)w)), never an fma, so that w = 0 and
+ *       w = 1 give an endpoint exactly; along x for the four rows (y0 z0, y1 z0, y0 z1, y1 z1), then along y, then along z;
+ *   the result is d as it is if all eight codes are 0 (-0.0 and a NaN stay), else (float)__dadd_rn((double)d, blend).
+ * In the PACKED form the two x-neighbours of a row come out of one pass over their group's planes wherever both lie in one cell and
+ * one group (adjacent lanes); at a cell boundary, in a row of a ragged cell that wraps a group and at the clamped upper face they are
+ * read one by one.  No unpacked copy and no per-chunk copy of codes is made in either form.  d_values is written by the evaluation
+ * first and corrected in place, chunk by chunk; the result does not depend on the chunk size.  A correction without flagged cells
+ * gives d.  A verbatim correction (kind 2) is refused by name: its codes are bit patterns, not residuals.
+ * Bounds.  The blend is a convex combination of the eight residuals.  With delta_a the distance of axis a's t from the nearest
+ * integer, the sample lies within (delta_x + delta_y + delta_z) * (max - min of the eight residuals) of d + residual(voxel), apart
+ * from the roundings above, where voxel is the one whose centre is nearest.  For FLOAT, d + residual(voxel) is the corrected voxel
+ * before its rounding to float, so at a voxel centre the sample is the corrected voxel.  For the integer types d is not rounded to
+ * the type, so at a voxel centre the field is within E + 0.5 of the original there.
+ *
+ * Both: stream as for DecodeToDevice (the library's stream waits for an event on the caller's; the call has completed on return);
+ * verify_params as for DecodeToDeviceCorrected.  Refusals, in this order, the first four groups before any device is initialised: a
+ * null correction; (SampleCorrected) a verbatim correction; a null pointer; d_voxels or d_coords not aligned to 4 bytes, d_out or
+ * d_values not aligned to the value type; a null volume; dims that differ from the volume's; a malformed VNR_AMD_DECODE_CHUNK.  Then
+ * n == 0 returns VNR_AMD_OK without touching a device.  Then: parameter count or hash under verify_params; a list or result that
+ * does not fit the allocation it points into; a voxel outside the grid.  A refused call has written nothing. */
+int  vnrAmdNeuralVolumeGatherVoxelsCorrected(vnrAmdVolume neural, vnrAmdCorrection, size_t n, const int32_t* d_voxels, void* d_out,
+                                             void* stream, int verify_params);
+int  vnrAmdNeuralVolumeSampleCorrected(vnrAmdVolume neural, vnrAmdCorrection, size_t n, const float* d_coords, float* d_values,
+                                       void* stream, int verify_params);
 /* hash-grid encode only (tcnn_impl_decoder.cu:177-230, column = level*F + f): fp16 [n][padded_width] */
 int    vnrAmdNeuralVolumeEncode(vnrAmdVolume, size_t n, const float* d_coords, uint16_t* d_features, void* stream);
 /* AMD extension: state of the brick image, the de-hashed inference copy of the hashed levels (csrc/grid_levels.h, csrc/brick_cache.h).  It is built

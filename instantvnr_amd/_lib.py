@@ -298,6 +298,8 @@ def lib():
     sig("vnrAmdCorrectionSerializeCoded", I, P, C.POINTER(P), C.POINTER(SZ))
     sig("vnrAmdCreateCorrectionFromCodedBytes", P, P, SZ)
     sig("vnrAmdCorrectionSerializeCodedToDevice", I, P, P, SZ, C.POINTER(SZ), P)
+    sig("vnrAmdNeuralVolumeGatherVoxelsCorrected", I, P, P, SZ, P, P, P, I)
+    sig("vnrAmdNeuralVolumeSampleCorrected", I, P, P, SZ, P, P, P, I)
     _lib = L
     return L
 

@@ -712,6 +712,42 @@ def vnrNeuralVolumeDecodeToDeviceCorrected(v, correction, d_ptr, strides=None, s
     check(lib().vnrAmdNeuralVolumeDecodeToDeviceCorrected(v.h, correction.h, C.c_void_p(ptr), s, C.c_void_p(stream) if stream else None, int(bool(verify_params))))
 
 
+def _list_arg(a, dtype, what):
+    """an (n, 3) DeviceArray of `dtype` -> (n, its address, or None for an empty list that holds no memory)"""
+    if not isinstance(a, DeviceArray) or a.dtype != np.dtype(dtype) or len(a.shape) != 2 or a.shape[1] != 3:
+        raise VnrAmdError(f"{what} must be a DeviceArray of {np.dtype(dtype).name} with shape (n, 3), got {getattr(a, 'dtype', type(a).__name__)} {getattr(a, 'shape', '')}")
+    return int(a.shape[0]), C.c_void_p(a.ptr) if a.ptr else None
+
+
+def _list_out(out, n, dtype):
+    if out is None:
+        return DeviceArray((n,), dtype)
+    if not isinstance(out, DeviceArray) or out.dtype != np.dtype(dtype) or int(np.prod(out.shape)) < n:
+        raise VnrAmdError(f"out must be a DeviceArray of at least {n} {np.dtype(dtype).name}, got {getattr(out, 'dtype', type(out).__name__)} {getattr(out, 'shape', '')}")
+    return out
+
+
+def vnrNeuralVolumeGatherVoxelsCorrected(v, correction, voxels, out=None, stream=None, verify_params=True):
+    """the corrected voxels at `voxels`, an int32 DeviceArray of shape (n, 3) of grid indices (x, y, z) in any order: element j is bit
+    for bit what vnrNeuralVolumeDecodeToDeviceCorrected stores there (include/vnr_amd.h, "random access to the corrected field"); only
+    those voxels are evaluated.  -> `out`, a DeviceArray of n elements of the correction's value type (made here if None)"""
+    n, p = _list_arg(voxels, np.int32, "voxels")
+    value_type = correction.info()["value_type"]
+    out = _list_out(out, n, next(dt for dt, t in VALUE_TYPES.items() if t == value_type))
+    check(lib().vnrAmdNeuralVolumeGatherVoxelsCorrected(v.h, correction.h, n, p, C.c_void_p(out.ptr), C.c_void_p(stream) if stream else None, int(bool(verify_params))))
+    return out
+
+
+def vnrNeuralVolumeSampleCorrected(v, correction, coords, out=None, stream=None, verify_params=True):
+    """the corrected field at `coords`, a float32 DeviceArray of shape (n, 3) of positions in [0, 1] as for neural_inference: the
+    network's value in the data units of the correction's range plus the trilinear blend of the stored residuals of the eight voxel
+    centres around each.  -> `out`, a float32 DeviceArray of n values (made here if None)"""
+    n, p = _list_arg(coords, np.float32, "coords")
+    out = _list_out(out, n, np.float32)
+    check(lib().vnrAmdNeuralVolumeSampleCorrected(v.h, correction.h, n, p, C.c_void_p(out.ptr), C.c_void_p(stream) if stream else None, int(bool(verify_params))))
+    return out
+
+
 def vnrNeuralVolumeSerializeParams(v, filename=None):
     """with a filename: writes BSON params.json; without: returns the BSON bytes"""
     if filename is not None:

@@ -794,6 +794,31 @@ int vnrAmdNeuralVolumeDecodeBoxToDeviceCorrected(vnrAmdVolume v, vnrAmdCorrectio
     n->decode_to_device_corrected(*k, DeviceTarget{d_out, k->data.h.value_type, strides, (hipStream_t)stream}, box_lo, box_size, verify_params != 0);
   });
 }
+int vnrAmdNeuralVolumeGatherVoxelsCorrected(vnrAmdVolume v, vnrAmdCorrection c, size_t n, const int32_t* d_voxels, void* d_out, void* stream, int verify_params)
+{
+  return guarded([&]() {
+    Correction* k = as_correction(c);   // (what needs no volume comes first)
+    if (!d_voxels) throw std::runtime_error("null voxel list");
+    if (!d_out) throw std::runtime_error("null device data");
+    const size_t ts = device_value_type_size(k->data.h.value_type);
+    if ((uintptr_t)d_voxels % sizeof(int32_t) != 0) throw std::runtime_error("the voxel list is not aligned to 4 bytes");
+    if ((uintptr_t)d_out % ts != 0) throw std::runtime_error("device data is not aligned to its value type (" + std::to_string(ts) + " bytes)");
+    as_neural(v)->gather_voxels_corrected(*k, n, d_voxels, d_out, (hipStream_t)stream, verify_params != 0);
+  });
+}
+int vnrAmdNeuralVolumeSampleCorrected(vnrAmdVolume v, vnrAmdCorrection c, size_t n, const float* d_coords, float* d_values, void* stream, int verify_params)
+{
+  return guarded([&]() {
+    Correction* k = as_correction(c);
+    if (k->data.h.kind == kCorrectionVerbatim)
+      throw std::runtime_error("a verbatim correction (kind 2, eps == 0) cannot be sampled: its codes are bit patterns, not residuals");
+    if (!d_coords) throw std::runtime_error("null coordinates");
+    if (!d_values) throw std::runtime_error("null device data");
+    if ((uintptr_t)d_coords % sizeof(float) != 0) throw std::runtime_error("the coordinates are not aligned to 4 bytes");
+    if ((uintptr_t)d_values % sizeof(float) != 0) throw std::runtime_error("device data is not aligned to its value type (4 bytes)");
+    as_neural(v)->sample_corrected(*k, n, d_coords, d_values, (hipStream_t)stream, verify_params != 0);
+  });
+}
 int vnrAmdCorrectionSetResidentForm(vnrAmdCorrection c, int form)
 {
   return guarded([&]() {

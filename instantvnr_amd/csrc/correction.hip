@@ -15,6 +15,10 @@
 // correction_rates_coded ("byte budgets in the coded form") is the same pass with the coded instantiation of both kernels, which adds
 // the exact size of the coded form per tolerance; tests/correction_coded_rate_ref.py restates that.
 //
+// gather_voxels_corrected and sample_corrected ("random access to the corrected field") take a list instead of a box, one lane a query:
+// the gather stores what the apply stores at the listed voxels (the box kernels' own voxel()), the sampler adds the trilinear blend of
+// the stored residuals of the eight voxel centres around a position to the network's value there; tests/correction_sample_ref.py.
+//
 // build_correction_packed ("corrections built straight into bit planes", at the end of this file) gives build_correction's correction
 // in the packed resident form without the fixed-width codes in between: the rate pass's walk for one tolerance with the error reports
 // taken from it, n_cells pairs through the host (correction_direct.cpp), an index kernel, and the planes of the groups that store any
@@ -183,6 +187,16 @@ __device__ __forceinline__ void store_code(uint8_t* payload, uint64_t offset, ui
   reinterpret_cast<C*>(payload + offset)[li] = (C)q;
 }
 
+// code li of a cell of the fixed-width payload (kinds 0 and 1), sign-extended; codes: the cell's first byte
+__device__ __forceinline__ int64_t load_code(const uint8_t* __restrict__ codes, uint32_t width, uint32_t li)
+{
+  return width == 1 ? (int64_t)reinterpret_cast<const int8_t*>(codes)[li]
+                    : (width == 2 ? (int64_t)reinterpret_cast<const int16_t*>(codes)[li] : (int64_t)reinterpret_cast<const int32_t*>(codes)[li]);
+}
+
+// the signed code of kinds 0 and 1 from its z of the packed form
+__device__ __forceinline__ int64_t unzigzag(uint64_t z) { return (int64_t)(z >> 1) ^ -(int64_t)(z & 1); }
+
 // ---- pass 2: the codes of the flagged cells, the error after --------------------------------------------------------------------------------
 template <typename T>
 struct EncodeOp {
@@ -284,9 +298,7 @@ struct ApplyOp {
         return v;
       }
     }
-    const int64_t q = en.width == 1 ? (int64_t)reinterpret_cast<const int8_t*>(codes)[li]
-                                    : (en.width == 2 ? (int64_t)reinterpret_cast<const int16_t*>(codes)[li] : (int64_t)reinterpret_cast<const int32_t*>(codes)[li]);
-    return corrected_value<T>(dec, q, k);
+    return corrected_value<T>(dec, load_code(codes, en.width, li), k);
   }
   __device__ __forceinline__ void one(T* p, uint64_t i)
   {
@@ -367,8 +379,7 @@ struct PlanesApplyOp {
         return v;
       }
     }
-    const int64_t q = (int64_t)(z >> 1) ^ -(int64_t)(z & 1);
-    return corrected_value<T>(dec, q, k);
+    return corrected_value<T>(dec, unzigzag(z), k);
   }
   // x, y, z: the voxel in the grid
   __device__ __forceinline__ T voxel(uint64_t i, uint32_t x, uint32_t y, uint32_t z)
@@ -425,6 +436,168 @@ __global__ void __launch_bounds__(kBlock) correction_apply_planes_kernel(T* __re
 {
   PlanesApplyOp<T> op{values, b, c, k, L.bx, L.by, g, ox, oy, oz, cells, groups, planes};
   for_each_chunk_voxel<T>(dst, L, b, e, op);
+}
+
+// ---- random access (include/vnr_amd.h, "random access to the corrected field"): a list instead of a box, one lane a query ---------------------
+// What the list calls read of a correction: kFormFixed and kFormPacked are the resident forms; kFormNone: no cell is flagged.
+constexpr int kFormFixed = 0, kFormPacked = 1, kFormNone = 2;
+
+struct CorrectionView {
+  const CorrectionTableEntry* __restrict__ table;
+  const uint8_t* __restrict__ payload;
+  const Correction::PlaneCell* __restrict__ cells;
+  const uint32_t* __restrict__ groups;
+  const uint64_t* __restrict__ planes;
+};
+
+// position j of the lowest voxel of the list outside the grid into *first_bad (the caller sets it to ~0): one ballot a wave, one
+// atomicMin a wave that holds such a voxel.  A negative component is a large unsigned one.
+__global__ void __launch_bounds__(kBlock) correction_voxels_check_kernel(const int32_t* __restrict__ voxels, uint64_t n, CellGrid g,
+                                                                         unsigned long long* __restrict__ first_bad)
+{
+  const uint32_t lane = threadIdx.x & 63u;
+  for (uint64_t base = (uint64_t)blockIdx.x * kBlock + (threadIdx.x & ~63u); base < n; base += (uint64_t)gridDim.x * kBlock) {   // (wave-uniform)
+    const uint64_t j = base + lane;
+    bool bad = false;
+    if (j < n) bad = (uint32_t)voxels[3 * j + 0] >= g.dx || (uint32_t)voxels[3 * j + 1] >= g.dy || (uint32_t)voxels[3 * j + 2] >= g.dz;
+    const uint64_t mask = __ballot(bad);
+    if (mask && lane == 0) atomicMin(first_bad, (unsigned long long)(base + (uint32_t)__ffsll((long long)mask) - 1u));
+  }
+}
+
+// the centres of the listed voxels: decode_coords_kernel's arithmetic
+__global__ void __launch_bounds__(kBlock) correction_voxel_coords_kernel(const int32_t* __restrict__ voxels, uint32_t n, vec3f rdims, float* __restrict__ coords)
+{
+  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= n) return;
+  coords[3 * (size_t)t + 0] = ((float)voxels[3 * (size_t)t + 0] + 0.5f) * rdims.x;
+  coords[3 * (size_t)t + 1] = ((float)voxels[3 * (size_t)t + 1] + 0.5f) * rdims.y;
+  coords[3 * (size_t)t + 2] = ((float)voxels[3 * (size_t)t + 2] + 0.5f) * rdims.z;
+}
+
+// out[t] = what the apply of this form stores at voxel t of the list: the very voxel() of the box kernels, the box at the origin
+template <typename T, int Form>
+__global__ void __launch_bounds__(kBlock) correction_gather_kernel(const int32_t* __restrict__ voxels, uint32_t n, const float* __restrict__ values, Conversion c,
+                                                                   Quantiser k, CellGrid g, CorrectionView v, T* __restrict__ out)
+{
+  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= n) return;
+  const uint32_t x = (uint32_t)voxels[3 * (size_t)t + 0], y = (uint32_t)voxels[3 * (size_t)t + 1], z = (uint32_t)voxels[3 * (size_t)t + 2];
+  if constexpr (Form == kFormFixed) {
+    ApplyOp<T> op{values, 0, c, k, 0, 0, g, 0, 0, 0, TableReader{v.table}, v.payload};
+    out[t] = op.voxel(t, x, y, z);
+  } else if constexpr (Form == kFormPacked) {
+    PlanesApplyOp<T> op{values, 0, c, k, 0, 0, g, 0, 0, 0, v.cells, v.groups, v.planes};
+    out[t] = op.voxel(t, x, y, z);
+  } else {
+    out[t] = convert_value<T>(values[t], c);
+  }
+}
+
+// where a coordinate lies between the voxel centres of its axis, in fp32: t = p dim - 0.5 clamped to [0, dim - 1] (a NaN: 0)
+struct AxisPlace { uint32_t i0, i1; float w; };
+
+__device__ __forceinline__ AxisPlace axis_place(float p, uint32_t dim)
+{
+  float t = __fsub_rn(__fmul_rn(p, (float)dim), 0.5f);
+  if (!(t >= 0.0f)) t = 0.0f;
+  const float top = (float)(dim - 1u);
+  if (t > top) t = top;
+  const float f = floorf(t);
+  const uint32_t i0 = (uint32_t)f;
+  return AxisPlace{i0, std::min(i0 + 1u, dim - 1u), __fsub_rn(t, f)};   // (the difference is exact)
+}
+
+// the codes of the two x-neighbours x0 <= x1 <= x0 + 1 of a row; a voxel of a cell that is not flagged has the code 0
+struct FixedRows {
+  CellGrid g;
+  TableReader table;
+  const uint8_t* __restrict__ payload;
+  __device__ __forceinline__ int64_t code(uint32_t x, uint32_t y, uint32_t z)
+  {
+    const CorrectionTableEntry& en = table.at(g.cell(x, y, z));
+    return en.offset == ~0ull ? 0 : load_code(payload + en.offset, en.width, g.local(x, y, z));
+  }
+  __device__ __forceinline__ void row(uint32_t x0, uint32_t x1, uint32_t y, uint32_t z, int64_t (&q)[2])
+  {
+    q[0] = code(x0, y, z);
+    q[1] = x1 == x0 ? q[0] : code(x1, y, z);
+  }
+};
+
+// in the packed form both come out of one pass over their group's planes wherever they are adjacent lanes of one group
+struct PlaneRows {
+  PlanesApplyOp<float> op;   // for its cached cell entry and its read_codes: a z of kinds 0 and 1 has at most 32 bits
+  __device__ __forceinline__ int64_t code(uint32_t x, uint32_t y, uint32_t z)
+  {
+    const Correction::PlaneCell& en = op.at(op.g.cell(x, y, z));
+    if (en.word0 == ~0ull) return 0;
+    uint32_t zc[1];
+    op.read_codes<1>(en, op.g.local(x, y, z), zc);
+    return unzigzag(zc[0]);
+  }
+  __device__ __forceinline__ void row(uint32_t x0, uint32_t x1, uint32_t y, uint32_t z, int64_t (&q)[2])
+  {
+    const uint32_t li = op.g.local(x0, y, z);
+    if (x1 != x0 && (x0 >> 4) == (x1 >> 4) && (li >> 6) == ((li + 1u) >> 6)) {
+      q[0] = q[1] = 0;
+      const Correction::PlaneCell& en = op.at(op.g.cell(x0, y, z));
+      if (en.word0 == ~0ull) return;
+      uint32_t zc[2];
+      op.read_codes<2>(en, li, zc);
+      q[0] = unzigzag(zc[0]); q[1] = unzigzag(zc[1]);
+    } else {   // the clamped upper face, a cell boundary, a row of a ragged cell that wraps a group: one by one
+      q[0] = code(x0, y, z);
+      q[1] = x1 == x0 ? q[0] : code(x1, y, z);
+    }
+  }
+};
+
+// the stored residual of a voxel as a double (kinds 0 and 1)
+__device__ __forceinline__ double code_residual(int64_t q, const Quantiser& k)
+{
+  if (k.kind == kCorrectionInteger) return (double)(std::max(-k.qmax, std::min(k.qmax, q)) * k.s);
+  return __dmul_rn((double)q, k.sd);
+}
+
+__device__ __forceinline__ double lerp_rn(double a, double b, double w)   // three roundings, never an fma; w = 0 or 1 gives an endpoint exactly
+{
+  return __dadd_rn(__dmul_rn(a, __dsub_rn(1.0, w)), __dmul_rn(b, w));
+}
+
+// values[t]: the network's value at coords[t] -> the corrected field there, in place: the converted value plus the trilinear blend of
+// the residuals of the eight surrounding voxel centres, x first, then y, then z.  All eight codes 0: the converted value as it is.
+template <int Form>
+__global__ void __launch_bounds__(kBlock) correction_sample_kernel(const float* __restrict__ coords, float* __restrict__ values, uint32_t n, Conversion c, Quantiser k,
+                                                                   CellGrid g, CorrectionView v)
+{
+  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= n) return;
+  const float d = convert_value<float>(values[t], c);
+  if constexpr (Form == kFormNone) {
+    values[t] = d;
+  } else {
+    const AxisPlace ax = axis_place(coords[3 * (size_t)t + 0], g.dx), ay = axis_place(coords[3 * (size_t)t + 1], g.dy), az = axis_place(coords[3 * (size_t)t + 2], g.dz);
+    int64_t q[4][2];   // the rows (y0, z0), (y1, z0), (y0, z1), (y1, z1)
+    if constexpr (Form == kFormFixed) {
+      FixedRows rows{g, TableReader{v.table}, v.payload};
+      rows.row(ax.i0, ax.i1, ay.i0, az.i0, q[0]); rows.row(ax.i0, ax.i1, ay.i1, az.i0, q[1]);
+      rows.row(ax.i0, ax.i1, ay.i0, az.i1, q[2]); rows.row(ax.i0, ax.i1, ay.i1, az.i1, q[3]);
+    } else {
+      PlaneRows rows{PlanesApplyOp<float>{nullptr, 0, c, k, 0, 0, g, 0, 0, 0, v.cells, v.groups, v.planes}};
+      rows.row(ax.i0, ax.i1, ay.i0, az.i0, q[0]); rows.row(ax.i0, ax.i1, ay.i1, az.i0, q[1]);
+      rows.row(ax.i0, ax.i1, ay.i0, az.i1, q[2]); rows.row(ax.i0, ax.i1, ay.i1, az.i1, q[3]);
+    }
+    int64_t any = 0;
+    double r[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      any |= q[i][0] | q[i][1];
+      r[i] = lerp_rn(code_residual(q[i][0], k), code_residual(q[i][1], k), (double)ax.w);
+    }
+    const double blend = lerp_rn(lerp_rn(r[0], r[1], (double)ay.w), lerp_rn(r[2], r[3], (double)ay.w), (double)az.w);
+    values[t] = any == 0 ? d : (float)__dadd_rn((double)d, blend);   // (-0.0 and a NaN's payload stay where nothing is stored)
+  }
 }
 
 // ---- the rate pass: the sizes many tolerances would build, from one evaluation of the network ----------------------------------------------
@@ -967,11 +1140,7 @@ void NeuralVolume::decode_to_device_corrected(Correction& corr, const DeviceTarg
   vec3i lower;
   const BoxLayout L = validate_box_array(out.data, h.value_type, out.strides, box_lo, box_size, grid, lower, h.range_lo, h.range_hi);
   const uint64_t chunk_limit = chunk_samples();
-  if (verify_params) {
-    if (h.n_params != (uint64_t)net_.n_params())
-      throw std::runtime_error("the correction was built on " + std::to_string(h.n_params) + " parameters, the volume has " + std::to_string(net_.n_params()));
-    if (h.params_hash != params_hash()) throw std::runtime_error("the volume's parameters are not the ones the correction was built on (their hash differs)");
-  }
+  if (verify_params) verify_correction_params(h);
   if (corr.data.cells.empty()) {   // nothing to apply: the plain decode
     decode_to_device(DeviceTarget{out.data, h.value_type, out.strides, out.consumer}, box_lo, box_size, nullptr, h.range_lo, h.range_hi);
     return;
@@ -1002,6 +1171,132 @@ void NeuralVolume::decode_to_device_corrected(Correction& corr, const DeviceTarg
     VNR_HIP_CHECK(hipGetLastError());
   }
   VNR_HIP_CHECK(hipStreamSynchronize(stream));   // on return the box is there
+}
+
+// ---- random access: the two list calls.  Their handles, pointers and alignments have been looked at by the entry points ----------------------
+namespace {
+
+// what both refuse before anything runs on a device; returns the chunk limit
+uint64_t list_call_check(const CorrectionHeader& h, vec3i grid)
+{
+  if (h.dims[0] != grid.x || h.dims[1] != grid.y || h.dims[2] != grid.z)
+    throw std::runtime_error("the correction's dims (" + std::to_string(h.dims[0]) + " x " + std::to_string(h.dims[1]) + " x " + std::to_string(h.dims[2]) +
+                             ") differ from the volume's (" + std::to_string(grid.x) + " x " + std::to_string(grid.y) + " x " + std::to_string(grid.z) + ")");
+  return chunk_samples();
+}
+
+// the form the kernels read and its pointers; a correction with a flagged cell has been made resident
+CorrectionView list_call_view(const Correction& corr, int& form)
+{
+  form = corr.empty() ? kFormNone : (corr.resident_form == 0 ? kFormFixed : kFormPacked);
+  if (form == kFormFixed) return CorrectionView{corr.d_table.ptr, corr.d_payload.ptr, nullptr, nullptr, nullptr};
+  if (form == kFormPacked) return CorrectionView{nullptr, nullptr, corr.d_plane_cells.ptr, corr.d_plane_groups.ptr, corr.d_planes()};
+  return CorrectionView{nullptr, nullptr, nullptr, nullptr, nullptr};
+}
+
+template <typename F>
+void dispatch_form(int form, F&& f)
+{
+  if (form == kFormFixed) f(std::integral_constant<int, kFormFixed>{});
+  else if (form == kFormPacked) f(std::integral_constant<int, kFormPacked>{});
+  else f(std::integral_constant<int, kFormNone>{});
+}
+
+}  // namespace
+
+void NeuralVolume::verify_correction_params(const CorrectionHeader& h)
+{
+  if (h.n_params != (uint64_t)net_.n_params())
+    throw std::runtime_error("the correction was built on " + std::to_string(h.n_params) + " parameters, the volume has " + std::to_string(net_.n_params()));
+  if (h.params_hash != params_hash()) throw std::runtime_error("the volume's parameters are not the ones the correction was built on (their hash differs)");
+}
+
+void NeuralVolume::gather_voxels_corrected(Correction& corr, size_t n, const int32_t* d_voxels, void* d_out, hipStream_t theirs, bool verify_params)
+{
+  const CorrectionHeader& h = corr.data.h;
+  const vec3i grid = desc.dims;
+  const uint64_t chunk = std::min<uint64_t>(list_call_check(h, grid), n);
+  if (n == 0) return;
+  if (!net_.valid()) throw std::runtime_error("neural volume has no valid network");
+  if (verify_params) verify_correction_params(h);
+  const size_t ts = device_value_type_size(h.value_type);
+  require_room(d_voxels, n * 3 * sizeof(int32_t), "the voxel list");
+  require_room(d_out, n * ts, "the result");
+  const CellGrid g = make_cell_grid(grid);
+  EventGuard ev;
+  wait_for(theirs, stream, ev);   // the list is complete, and what the destination held has been read, once the caller's stream reaches this point
+
+  // the whole list is looked at before a voxel is evaluated
+  dd_partials_.ensure(1);
+  unsigned long long* d_first_bad = (unsigned long long*)dd_partials_.ptr;
+  unsigned long long first_bad = ~0ull;
+  VNR_HIP_CHECK(hipMemsetAsync(d_first_bad, 0xff, sizeof(first_bad), stream));
+  const uint32_t check_blocks = (uint32_t)std::min<uint64_t>((n + kBlock - 1) / kBlock, (uint64_t)Runtime::get().n_cus * 8);
+  correction_voxels_check_kernel<<<check_blocks, kBlock, 0, stream>>>(d_voxels, n, g, d_first_bad);
+  VNR_HIP_CHECK(hipGetLastError());
+  VNR_HIP_CHECK(hipMemcpyAsync(&first_bad, d_first_bad, sizeof(first_bad), hipMemcpyDeviceToHost, stream));
+  VNR_HIP_CHECK(hipStreamSynchronize(stream));
+  if (first_bad != ~0ull) {
+    int32_t v[3];
+    VNR_HIP_CHECK(hipMemcpyAsync(v, d_voxels + 3 * first_bad, sizeof(v), hipMemcpyDeviceToHost, stream));
+    VNR_HIP_CHECK(hipStreamSynchronize(stream));
+    throw std::runtime_error("voxel " + std::to_string(first_bad) + " of the list (" + std::to_string(v[0]) + ", " + std::to_string(v[1]) + ", " + std::to_string(v[2]) +
+                             ") is outside the grid " + std::to_string(grid.x) + " x " + std::to_string(grid.y) + " x " + std::to_string(grid.z));
+  }
+
+  if (!corr.empty()) correction_make_resident(corr, corr.resident_form, stream);
+  int form;
+  const CorrectionView view = list_call_view(corr, form);
+  const vec3f rdims = {1.0f / (float)grid.x, 1.0f / (float)grid.y, 1.0f / (float)grid.z};
+  const Conversion c{h.range_lo, h.range_hi - h.range_lo, h.range_lo < h.range_hi};
+  const Quantiser k = make_quantiser(h.kind, h.eps);
+  dd_coords_.ensure(3 * chunk);
+  dd_values_.ensure(chunk);
+  for (uint64_t b = 0; b < n; b += chunk) {
+    const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, n - b), blocks = div_round_up(m, kBlock);
+    const int32_t* voxels = d_voxels + 3 * b;
+    correction_voxel_coords_kernel<<<blocks, kBlock, 0, stream>>>(voxels, m, rdims, dd_coords_.ptr);
+    VNR_HIP_CHECK(hipGetLastError());
+    net_.inference(dd_coords_.ptr, dd_values_.ptr, m, nullptr, m, stream);
+    dispatch_type(h.value_type, [&](auto* tag) {
+      using T = std::remove_pointer_t<decltype(tag)>;
+      dispatch_form(form, [&](auto f) {
+        correction_gather_kernel<T, decltype(f)::value><<<blocks, kBlock, 0, stream>>>(voxels, m, dd_values_.ptr, c, k, g, view, (T*)d_out + b);
+      });
+    });
+    VNR_HIP_CHECK(hipGetLastError());
+  }
+  VNR_HIP_CHECK(hipStreamSynchronize(stream));   // on return the values are there
+}
+
+void NeuralVolume::sample_corrected(Correction& corr, size_t n, const float* d_coords, float* d_values, hipStream_t theirs, bool verify_params)
+{
+  const CorrectionHeader& h = corr.data.h;
+  const vec3i grid = desc.dims;
+  const uint64_t chunk = std::min<uint64_t>(list_call_check(h, grid), n);
+  if (n == 0) return;
+  if (!net_.valid()) throw std::runtime_error("neural volume has no valid network");
+  if (verify_params) verify_correction_params(h);
+  require_room(d_coords, n * 3 * sizeof(float), "the coordinates");
+  require_room(d_values, n * sizeof(float), "the result");
+  if (!corr.empty()) correction_make_resident(corr, corr.resident_form, stream);
+  int form;
+  const CorrectionView view = list_call_view(corr, form);
+  const Conversion c{h.range_lo, h.range_hi - h.range_lo, h.range_lo < h.range_hi};
+  const Quantiser k = make_quantiser(h.kind, h.eps);
+  const CellGrid g = make_cell_grid(grid);
+  EventGuard ev;
+  wait_for(theirs, stream, ev);
+  for (uint64_t b = 0; b < n; b += chunk) {
+    const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, n - b), blocks = div_round_up(m, kBlock);
+    net_.inference(d_coords + 3 * b, d_values + b, m, nullptr, m, stream);   // what vnrAmdNeuralVolumeInference gives, corrected in place
+    if (form == kFormNone && !c.scale) continue;   // no flagged cell and no range: the inference as it stands
+    dispatch_form(form, [&](auto f) {
+      correction_sample_kernel<decltype(f)::value><<<blocks, kBlock, 0, stream>>>(d_coords + 3 * b, d_values + b, m, c, k, g, view);
+    });
+    VNR_HIP_CHECK(hipGetLastError());
+  }
+  VNR_HIP_CHECK(hipStreamSynchronize(stream));   // on return the values are there
 }
 
 // ---- the direct build: field and network -> resident planes plus index, no fixed-width code in between ----------------------------------------

@@ -110,6 +110,7 @@ struct DecodeError {
   double sum_abs, sum_sq, psnr_db;
 };
 
+struct CorrectionHeader;   // correction_format.h
 struct Correction;   // an error-bound correction: correction_record.h (what it holds), correction_store.hip (its conversions)
 
 // guided_sampler.hip: the hierarchical inclusive scan of n uint64 in place (block scans, the block sums scanned the same way level by
@@ -292,6 +293,14 @@ public:
   // code is ever formed and no code crosses to the host.
   std::shared_ptr<Correction> build_correction_packed(const DeviceSource& ref, float range_lo, float range_hi, double eps);
   void decode_to_device_corrected(Correction& corr, const DeviceTarget& out, const int box_lo[3], const int box_size[3], bool verify_params);
+  // Random access to the corrected field (correction.hip; include/vnr_amd.h spells the arithmetic out), a lane a query, in chunks of
+  // VNR_AMD_DECODE_CHUNK.  gather_voxels_corrected: d_out[j] = what decode_to_device_corrected stores at voxel d_voxels[j] (n x {x, y, z}
+  // of the volume's grid, any order, duplicates allowed), only those voxels evaluated, through the decode's scratch; the whole list is
+  // validated on the device before the first evaluation.  sample_corrected: d_values[j] = the network's value at d_coords[j] in data
+  // units plus the trilinear blend of the stored residuals of the eight voxel centres around it, evaluated into d_values and corrected
+  // in place.  Handles, pointers, alignment and the kind are the entry points' to check; `theirs` is the caller's stream.
+  void gather_voxels_corrected(Correction& corr, size_t n, const int32_t* d_voxels, void* d_out, hipStream_t theirs, bool verify_params);
+  void sample_corrected(Correction& corr, size_t n, const float* d_coords, float* d_values, hipStream_t theirs, bool verify_params);
   // correction_rates: for each of n_eps (1 .. 64) tolerances exactly the counts and the sizes in both serialised forms that
   // build_correction(ref, range, eps[k]) would give, from ONE chunked evaluation of the network; nothing is built, `ref` is only read,
   // and only the n_eps results cross to the host (out: host memory).
@@ -314,6 +323,7 @@ public:
   hipStream_t stream;
 
 private:
+  void verify_correction_params(const CorrectionHeader& h);   // throws unless count and hash of the parameters are the header's
   void rate_pass(const DeviceSource& ref, float range_lo, float range_hi, const double* eps, int n_eps, CorrectionRate* out, uint64_t* coded_words);
   SimpleVolume* source_ = nullptr;
   std::shared_ptr<void> source_keepalive_;

@@ -47,6 +47,11 @@ ingest time are printed.
                          (vnrAmdNeuralVolumeDecodeBoxToDeviceCorrected), check it on the host against the step's own array (every
                          voxel within max_abs_after) and against the same box cut out of the whole-grid corrected decode (equal
                          bytes), and time it beside the plain vnrAmdNeuralVolumeDecodeToDevice of the box
+  --probe N              with --error-bound: after the build draw N seeded voxels and N seeded points.  The voxels go through
+                         vnrAmdNeuralVolumeGatherVoxelsCorrected: the largest |gather - original| on the host beside the correction's
+                         max_abs_after, and whether the values are the whole-grid corrected decode's at those voxels; the points
+                         through vnrAmdNeuralVolumeSampleCorrected (not for EPS = 0 on a float type: a verbatim correction has no
+                         residuals).  Both calls timed, in the form --resident sets
   --byte-budget BYTES    after each step's training: the correction of the tightest tolerance the search finds whose serialised
                          size is at most BYTES (vnrAmdNeuralVolumeBuildCorrectionWithinBytes).  eps_hi is the step's max_abs from
                          the error report (vnrAmdNeuralVolumeErrorAgainstDevice), at which nothing is flagged.  Per step: the chosen
@@ -106,6 +111,11 @@ correction_direct_index_kernel, correction_direct_list_kernel and correction_dir
 
 The --roi times are host clocks around whole calls as well, each warmed up once: "roi_apply" evaluates the network for the box's
 voxels alone and applies the correction in the resident form, "roi_plain_decode" is DecodeToDevice of the same box.
+
+The --probe times are host clocks around whole calls, each warmed up once: "probe_gather" validates the list, evaluates the network
+for the listed voxels alone and applies the correction to them (correction_voxels_check_kernel, correction_voxel_coords_kernel,
+correction_gather_kernel), "probe_sample" evaluates the network at the points and blends the stored residuals of the eight voxel
+centres around each (correction_sample_kernel).
 
 The --byte-budget times are host clocks around whole calls, each warmed up once: "budget_ms" is the whole
 vnrAmdNeuralVolumeBuildCorrectionWithinBytes (1 + rounds rate passes at most, one build, for the packed form the device pack),
@@ -188,9 +198,9 @@ def round_trip(neural, ptr, dtype, strides, dims, ghost, value_range, repeat, co
     return row
 
 
-def error_bound(neural, ptr, dtype, strides, dims, ghost, value_range, eps, repeat, packed=False, resident="fixed", roi=None, step=None):
+def error_bound(neural, ptr, dtype, strides, dims, ghost, value_range, eps, repeat, packed=False, resident="fixed", roi=None, step=None, probe=0, seed=1):
     """-> the --error-bound columns of one step.  `ptr` is the step's own device array (the reference of the correction), `step`
-    the same voxels on the host (for --roi)."""
+    the same voxels on the host (for --roi and --probe)."""
     def build():
         c = api.vnrNeuralVolumeBuildCorrection(neural, ptr, dtype, eps, strides, value_range)
         held.append(c)
@@ -225,6 +235,23 @@ def error_bound(neural, ptr, dtype, strides, dims, ghost, value_range, eps, repe
         _, best, median = timed(lambda: api.vnrNeuralVolumeDecodeToDevice(neural, box, dtype, None, roi, None, value_range), repeat, 1)
         row.update(roi_plain_decode_ms=round(best, 4), roi_plain_decode_median_ms=round(median, 4))
         box.free()
+    if probe:
+        rng = np.random.default_rng(seed)
+        voxels = np.stack([rng.integers(0, dims[a], probe) for a in range(3)], axis=1).astype(np.int32)
+        d_voxels, d_got = api.DeviceArray.from_numpy(voxels), api.DeviceArray((probe,), dtype)
+        _, best, median = timed(lambda: api.vnrNeuralVolumeGatherVoxelsCorrected(neural, corr, d_voxels, d_got, verify_params=False), repeat, 1)
+        got = d_got.numpy()
+        at = (voxels[:, 2], voxels[:, 1], voxels[:, 0])
+        whole = out.numpy()[ghost:ghost + dims[2], ghost:ghost + dims[1], ghost:ghost + dims[0]]
+        row.update(probe=probe, probe_gather_ms=round(best, 4), probe_gather_median_ms=round(median, 4),
+                   probe_max_abs_error=float(np.abs(got.astype(np.float64) - step[at].astype(np.float64)).max()),
+                   probe_equals_whole_grid=bool(np.array_equal(got.view(np.uint8), np.ascontiguousarray(whole[at]).view(np.uint8))))
+        d_voxels.free(); d_got.free()
+        if info["kind"] != 2:
+            d_points, d_values = api.DeviceArray.from_numpy(rng.uniform(0.0, 1.0, (probe, 3)).astype(np.float32)), api.DeviceArray((probe,), np.float32)
+            _, best, median = timed(lambda: api.vnrNeuralVolumeSampleCorrected(neural, corr, d_points, d_values, verify_params=False), repeat, 1)
+            row.update(probe_sample_ms=round(best, 4), probe_sample_median_ms=round(median, 4))
+            d_points.free(); d_values.free()
     _, best, median = timed(lambda: api.vnrNeuralVolumeDecodeToDevice(neural, out.ptr + first, dtype, strides, None, None, value_range), repeat, 1)
     row.update(plain_decode_ms=round(best, 4), plain_decode_median_ms=round(median, 4))
     _, best, median = timed(lambda: api.vnrNeuralVolumeErrorAgainstDevice(neural, ptr, dtype, strides, None, value_range), repeat, 1)
@@ -455,6 +482,7 @@ def main(argv=None):
     p.add_argument("--coded", action="store_true")
     p.add_argument("--resident", default="fixed", choices=["fixed", "packed"])
     p.add_argument("--roi", default=None, metavar="x0,y0,z0,sx,sy,sz")
+    p.add_argument("--probe", type=int, default=0, metavar="N")
     p.add_argument("--byte-budget", type=int, default=None, metavar="BYTES")
     p.add_argument("--budget-form", default="packed", choices=["fixed", "packed", "coded"])
     p.add_argument("--budget-rounds", type=int, default=2, metavar="N")
@@ -474,9 +502,9 @@ def main(argv=None):
     if a.byte_budget is not None and (not a.steps_per_frame or a.byte_budget < 0 or not 0 <= a.budget_rounds <= 8):
         p.error("--byte-budget needs a trained network (--steps-per-frame > 0), BYTES >= 0 and --budget-rounds 0 .. 8")
     roi = None
-    if a.roi is not None or a.resident != "fixed":
-        if a.error_bound is None:
-            p.error("--resident and --roi need --error-bound EPS")
+    if a.roi is not None or a.resident != "fixed" or a.probe:
+        if a.error_bound is None or a.probe < 0:
+            p.error("--resident, --roi and --probe N (N > 0) need --error-bound EPS")
     if a.roi is not None:
         try:
             v = [int(x) for x in a.roi.split(",")]
@@ -535,7 +563,7 @@ def main(argv=None):
             if a.round_trip:     # in data units: the range that was applied inverts the ingest
                 row.update(round_trip(neural, ptr, dtype, strides, dims, a.ghost, used, a.repeat, coords))
             if a.error_bound is not None:
-                row.update(error_bound(neural, ptr, dtype, strides, dims, a.ghost, used, a.error_bound, a.repeat, a.packed, a.resident, roi, step))
+                row.update(error_bound(neural, ptr, dtype, strides, dims, a.ghost, used, a.error_bound, a.repeat, a.packed, a.resident, roi, step, a.probe, a.seed))
                 if a.direct:
                     row.update(direct_build(neural, ptr, dtype, strides, used, a.error_bound, a.repeat))
                 if a.coded:
